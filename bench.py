@@ -37,14 +37,35 @@ the raw count (every series of every completed read). The reference ingests 5 se
 per GPU per 5 s refresh (<= 1.0 sample/s/GPU), so ``vs_baseline`` =
 value / (N * 1.0). ``p50_refresh_ms`` (from the start of the oldest source's newest read
 to the frame payload) is compared with the reference's measured p50 full-refresh latency
-at the same N. After the timed region an untimed
+at the same N.
+
+A plain run does only what that headline needs: it sets up, warms up, times the K steps,
+writes its outputs if ``--dump-outputs DIR`` is given, and prints the line. Everything
+below is a side measurement with a run of its own and happens only with ``--full``.
+
+``--full``: after the timed region the same refreshes continue untimed for
+``--cpu-window-s`` (``cpu_seconds_per_s`` over a window the kernel's CPU accounting
+resolves), and an untimed
 side run of ``--timing-steps`` refreshes records HIP events around the stats kernel,
 the native ncclAllGather and the publish kernel - the same native path the timed region
 runs at N > 1 and the node service runs (one-rank communicator at N = 1):
 ``device_us_p50``. Then ``--e2e-s`` seconds of the DEPLOYED path, run collectively by the
 job's own ranks at production sampling rates (rocmdash/runtime/deployed.py): service
 refresh -> /metrics -> mini-Prometheus -> the page's queries -> frame, reported as
-``prometheus_page_p50_ms`` and ``display_age_p50_ms`` (the path users see).
+``prometheus_page_p50_ms`` and ``display_age_p50_ms`` (the path users see). Once every
+rank has exited, rank 0's parent measures the production node service for
+``--production-s`` seconds (``production_node``) and the lean runtime environment
+(``lean_env``). Without ``--full`` these fields of the line are null or absent.
+
+``--dump-outputs DIR``: live telemetry differs from run to run, so after the timed steps
+(and any side run) the sources are stopped, every ring's window is replaced by generated
+rows from a fixed seed, and the timed path - ``NodePipeline.step()``, the call the timed
+loop makes - runs ``DUMP_STEPS`` more refreshes over a few more seeded rows each (a full
+re-sort first, then the steady-state path). Rank 0 writes what the last of them computed:
+``DIR/node_stats.npy`` (float32 [N, S, 8], the gathered statistics the frame is rendered
+from), ``DIR/frame_numbers.npy`` (float64: every number of the frame's figures and stats
+table, in document order) and, with ``--node-window``, ``DIR/node_window_stats.npy``.
+The same arguments give the same inputs, so two builds can be compared output for output.
 
 Process layout: the process the launcher starts for a rank never touches the GPU; it
 runs the measurement in a child process. A child that finds its device-counter reads
@@ -56,7 +77,7 @@ the node refresh is paced by its slowest GPU, and at 8 ranks restarting every ra
 rarely end all fast. The JSON line reports ``startup_restarts`` (per rank in
 ``startup_restarts_by_rank`` / ``ranks[].attempt``).
 
-Run: python bench.py [--gpus N --steps K --warmup W]. For N > 1 either under
+Run: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]. For N > 1 either under
 torch.distributed.run (one rank per GPU, RCCL), or without a launcher: the process then
 starts the N rank processes itself (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR /
 MASTER_PORT, as the launcher would set them; it never touches the GPU) and exits with the
@@ -81,6 +102,58 @@ import time
 REF_P50_MS = {1: 39.95, 2: 56.04, 4: 85.97, 8: 154.53}
 REF_SAMPLES_PER_S_PER_GPU = 1.0
 METRIC = "metric samples/sec/GPU + p50 dashboard refresh latency at 1/2/4/8 MI355X"
+
+
+# the side measurements (each a run of its own) and their length under --full
+FULL_DEFAULTS = {"timing_steps": 100, "cpu_window_s": 1.0, "e2e_s": 5.0, "production_s": 10.0}
+DUMP_SEED = 20240607  # --dump-outputs: the generated rows' seed
+DUMP_STEPS = 4  # --dump-outputs: refreshes over the seeded window (the last one is written)
+
+
+def _add_side_run_options(ap) -> None:
+    """``--full`` and the side measurements it turns on (shared by the rank parents'
+    parser and the measurement's own)."""
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the timed region: CPU window, HIP-event side run, "
+                    "deployed path, production node service and lean runtime environment (off: a plain run "
+                    "sets up, warms up, times --steps refreshes and prints the line)")
+    ap.add_argument("--timing-steps", type=int, default=None,
+                    help="--full: untimed side run after the timed region with HIP events around the stats kernel "
+                    "and the all-gather (default 100; 0 = skip)")
+    ap.add_argument("--production-s", type=float, default=None,
+                    help="--full: after every measurement rank has exited, seconds of the PRODUCTION node service (the "
+                    "DaemonSet's supervisor + ranks + node counter process at amd-smi 10 Hz / counters 100 Hz) on "
+                    "the same GPUs, measured from outside - node-total CPU-s/s, counter rows per GPU, per-process "
+                    "PSS, per-rank HBM (production_node; default 10; 0 = skip; needs the restart parent)")
+    ap.add_argument("--cpu-window-s", type=float, default=None,
+                    help="--full: after the timed region, the same refreshes continue untimed this long to measure "
+                    "the mode's CPU-s/s (cpu_seconds_per_s; default 1; 0 = over the timed region only)")
+    ap.add_argument("--e2e-s", type=float, default=None,
+                    help="--full: after the timed region, seconds of the deployed path (service refresh 10 Hz -> "
+                    "/metrics -> mini-Prometheus scrape 0.25 s -> page queries -> frame), run by every rank "
+                    "(default 5; 0 = skip)")
+
+
+def _resolve_side_runs(ns) -> str | None:
+    """Fill in the side measurements' lengths: their --full defaults, or 0 in a plain
+    run. Returns an error text when a plain run asks for one of them."""
+    for k, dflt in FULL_DEFAULTS.items():
+        v = getattr(ns, k)
+        if ns.full:
+            setattr(ns, k, dflt if v is None else v)
+        elif v:
+            return f"--{k.replace('_', '-')} {v:g} is a side measurement: it needs --full"
+        else:
+            setattr(ns, k, type(dflt)(0))
+    return None
+
+
+def _side_run_args(argv_list):
+    """(namespace with the side measurements resolved, error text or None)."""
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)  # "--cpu" is not "--cpu-window-s"
+    _add_side_run_options(ap)
+    ns, _ = ap.parse_known_args(argv_list)
+    return ns, _resolve_side_runs(ns)
 
 
 def _interp_ref(n: int) -> float:
@@ -175,6 +248,70 @@ def _device_timing(agent, env, agg0, args):
     out["gather_validated"] = pipe.gather_report()["validated"]
     out["collectives_issued"] = agg.collectives
     return out, agg
+
+
+def _frame_numbers(payload) -> list:
+    """Every number in the frame's figures and stats table, in document order (the
+    ``updated`` clock text is not one)."""
+    frame = json.loads(payload)
+    out = []
+
+    def walk(o):
+        if isinstance(o, bool):
+            out.append(float(o))
+        elif isinstance(o, (int, float)):
+            out.append(float(o))
+        elif o is None:
+            out.append(float("nan"))
+        elif isinstance(o, dict):
+            for k in o:
+                walk(o[k])
+        elif isinstance(o, (list, tuple)):
+            for v in o:
+                walk(v)
+
+    walk(frame.get("figures"))
+    walk(frame.get("stats"))
+    return out
+
+
+def _dump_outputs(directory, agent, pipe, nws, args, sync) -> dict | None:
+    """``--dump-outputs``: run the timed path over seeded rows and write what its last
+    refresh computed (module docstring). Every rank runs the refreshes (they gather);
+    rank 0 writes the files and returns {name: shape}."""
+    import numpy as np
+
+    agent.wait_sample()
+    pipe.stop_sampling()
+    agent.stop()
+    # the whole window of every ring from the seed: the next refresh re-sorts it in full
+    agent.prefill_bulk(args.window, seed=DUMP_SEED)
+    rng = np.random.default_rng(DUMP_SEED + 1 + 7919 * agent.device_index)
+    t = time.time_ns()
+    payload = node_st = None
+    for i in range(DUMP_STEPS):
+        k = 1 + i % 3  # a few entering rows: the steady-state path of the timed loop
+        for r in agent.rings:
+            x = rng.normal(50.0, 10.0, (k, r.width)).astype(np.float32)
+            x[:, ::2] = np.rint(x[:, ::2])
+            r.push_many(x, np.arange(t, t + k, dtype=np.uint64))
+        t += k
+        payload, _ = pipe.step(sample=False)
+        if nws is not None:
+            node_st = nws.refresh()
+    sync()
+    snap = pipe.latest_snapshot()  # the same window again (no new rows): the gathered [N, S, 8]
+    sync()
+    if not pipe.is_root:
+        return None
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"node_stats": np.array(snap.window, dtype=np.float32),
+              "frame_numbers": np.array(_frame_numbers(payload), dtype=np.float64)}
+    if node_st is not None:
+        arrays["node_window_stats"] = node_st.detach().cpu().numpy().astype(np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 EXIT_SLOW_STATE = 75  # child: the device-counter reads came up in the slow driver state
@@ -341,10 +478,11 @@ def _run_with_restarts(argv) -> int:
     args_list = list(sys.argv[1:] if argv is None else argv)
     ap = argparse.ArgumentParser(add_help=False)
     ap.add_argument("--restarts", type=int, default=2)
-    ap.add_argument("--production-s", type=float, default=10.0)
     ap.add_argument("--json-out", default=None)
     ap.add_argument("--cpu", action="store_true")
+    _add_side_run_options(ap)
     known, _ = ap.parse_known_args(args_list)
+    _resolve_side_runs(known)  # main() has refused a plain run that asks for a side measurement
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     store = _parents_group(world, rank)
     line_file = None
@@ -422,11 +560,11 @@ def _lean_env_block(timeout_s: float = 240.0) -> dict:
     env["ROCMDASH_BENCH_RESTARTS"] = "0"  # measured in this process, no restart parent
     fd, path = tempfile.mkstemp(prefix="rocmdash-bench-lean-", suffix=".json")
     os.close(fd)
-    block = {"env": dict(LEAN_RUNTIME_ENV), "config": "python bench.py --gpus 1 --steps 20 --warmup 5 --e2e-s 3 "
-             "(rank 0's GPU), one process under the supervisor's runtime environment", "error": None}
+    block = {"env": dict(LEAN_RUNTIME_ENV), "config": "python bench.py --gpus 1 --steps 20 --warmup 5 --full --e2e-s 3 "
+             "--production-s 0 (rank 0's GPU), one process under the supervisor's runtime environment", "error": None}
     try:
         res = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "20", "--warmup",
-                              "5", "--e2e-s", "3", "--production-s", "0", "--json-out", path], env=env,
+                              "5", "--full", "--e2e-s", "3", "--production-s", "0", "--json-out", path], env=env,
                              capture_output=True, text=True, timeout=timeout_s)
         with open(path) as f:
             txt = f.read().strip()
@@ -450,8 +588,6 @@ def _lean_env_block(timeout_s: float = 240.0) -> dict:
 
 def _restart_rounds(args_list, known, world: int, rank: int, store) -> int:
     """The start-up rounds of _run_with_restarts; returns the measurement child's code."""
-    import torch
-
     attempt = 0
     p, verdict_r, decision_w = _start_child(args_list, attempt, known.restarts == 0, store)
     code = None
@@ -463,6 +599,7 @@ def _restart_rounds(args_list, known, world: int, rank: int, store) -> int:
             code = {"ok": 0, "slow": 1}.get(verdict, 2)
         codes, attempts = [code], [attempt]
         if store is not None:
+            import torch
             import torch.distributed as dist
 
             t = torch.tensor([code, attempt], dtype=torch.int64)
@@ -667,6 +804,10 @@ def _check_node_size(argv_list) -> int | None:
 
 def main(argv=None) -> int:
     argv_list = sys.argv[1:] if argv is None else argv
+    _, side_err = _side_run_args(argv_list)
+    if side_err:
+        print(f"[bench] error: {side_err}", file=sys.stderr)
+        return EXIT_USAGE
     if os.environ.get("ROCMDASH_BENCH_CHILD") is None and os.environ.get("ROCMDASH_BENCH_LAUNCHED") is None:
         stop = _check_node_size(argv_list)
         if stop is not None:
@@ -714,15 +855,7 @@ def main(argv=None) -> int:
                     "all-gather; N > 1 always gathers")
     ap.add_argument("--world1-group", type=int, default=1,
                     help="N = 1: create the one-rank RCCL group (for --gather rccl and the side run's gather timing)")
-    ap.add_argument("--timing-steps", type=int, default=100,
-                    help="untimed side run after the timed region with HIP events around the stats kernel and the "
-                    "all-gather (0 = skip)")
     ap.add_argument("--json-out", default=None)
-    ap.add_argument("--production-s", type=float, default=10.0,
-                    help="after every measurement rank has exited: seconds of the PRODUCTION node service (the "
-                    "DaemonSet's supervisor + ranks + node counter process at amd-smi 10 Hz / counters 100 Hz) on "
-                    "the same GPUs, measured from outside - node-total CPU-s/s, counter rows per GPU, per-process "
-                    "PSS, per-rank HBM (production_node; 0 = skip; needs the restart parent)")
     ap.add_argument("--restarts", type=int, default=2,
                     help="N = 1: start the measurement again (in a fresh child process) at most this many times when "
                     "its device-counter reads came up in the slow driver state (ROCMDASH_BENCH_RESTARTS=0: never)")
@@ -732,12 +865,11 @@ def main(argv=None) -> int:
     ap.add_argument("--slow-factor", type=float, default=1.4,
                     help="slow state = counter-read p50 above this multiple of the placement calibration's fast node "
                     "(the slow state reads 1.7-1.9x, a normal start ~1.0x)")
-    ap.add_argument("--cpu-window-s", type=float, default=1.0,
-                    help="after the timed region, the same refreshes continue untimed this long to measure the mode's "
-                    "CPU-s/s (cpu_seconds_per_s; 0 = over the timed region only)")
-    ap.add_argument("--e2e-s", type=float, default=5.0,
-                    help="after the timed region: seconds of the deployed path (service refresh 10 Hz -> /metrics -> "
-                    "mini-Prometheus scrape 0.25 s -> page queries -> frame), run by every rank (0 = skip)")
+    _add_side_run_options(ap)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, run the timed path over a seeded window and write what its last "
+                    "refresh computed as DIR/<name>.npy (same arguments, same inputs: builds compare output for "
+                    "output)")
     ap.add_argument("--collective-timeout", type=float,
                     default=float(os.environ.get("ROCMDASH_COLLECTIVE_TIMEOUT", "120")),
                     help="seconds a native gather may wait for the slowest rank before the job fails")
@@ -748,6 +880,7 @@ def main(argv=None) -> int:
                     help="experiment only: rank 0 renders a frame for this many GPUs (repeating the gathered ones); "
                     "the JSON line is marked 'rehearsal' and is not a measurement of that node size")
     args = ap.parse_args(argv)
+    _resolve_side_runs(args)  # checked above
 
     # Counters must be registered before the HIP runtime initialises.
     from rocmdash.runtime import native
@@ -987,6 +1120,9 @@ def main(argv=None) -> int:
         deployed = run_deployed_path(agent, tagg if tagg.collective else agg, seconds=args.e2e_s,
                                      collective_timeout_s=args.collective_timeout)
     dep = deployed or {}
+    dumped = None
+    if args.dump_outputs:
+        dumped = _dump_outputs(args.dump_outputs, agent, pipe, nws, args, sync)
     ms_per_step = elapsed / args.steps * 1e3
     lat_sorted = sorted(lat)
     p50 = statistics.median(lat_sorted)
@@ -1005,6 +1141,8 @@ def main(argv=None) -> int:
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(ms_per_step, 4),
+            "full": bool(args.full),
+            "dumped_outputs": dumped,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": round(value / (n * REF_SAMPLES_PER_S_PER_GPU), 2),

@@ -30,9 +30,6 @@ def cuda():
     return torch.device("cuda", 0)
 
 
-REFERENCE_APP = "/root/reference/app.py"
-
-
 @pytest.fixture
 def st_stub(monkeypatch):
     """The recording Streamlit double, importable as ``streamlit``."""
@@ -45,16 +42,10 @@ def st_stub(monkeypatch):
     sys.modules.pop("streamlit", None)
 
 
-@pytest.fixture
-def reference_app(st_stub):
-    """The reference app.py imported behind the Streamlit double (behavioural parity
-    oracle; skipped where the read-only reference checkout is absent)."""
-    import importlib.util
+@pytest.fixture(scope="session")
+def reference_golden():
+    """What the reference app.py did on the parity tests' inputs, as recorded in
+    tests/golden/reference_app.json.gz (behavioural parity oracle; tests/_golden.py)."""
+    import _golden
 
-    if not os.path.exists(REFERENCE_APP):
-        pytest.skip("reference checkout not present")
-    spec = importlib.util.spec_from_file_location("reference_app", REFERENCE_APP)
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    st_stub.reset()
-    return mod
+    return _golden.load()

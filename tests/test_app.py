@@ -1,6 +1,7 @@
 """The Streamlit page driven through the recording Streamlit double, side by side with
-the reference app.py on the same synthetic Prometheus data: same call sequence,
-same figures (JSON-equal), same headers, statistics and widget keys."""
+what the reference app.py did on the same synthetic Prometheus data (recorded in
+tests/golden/, tests/_golden.py): same call sequence, same figures (JSON-equal), same
+headers, statistics and widget keys."""
 
 import importlib.util
 import json
@@ -15,10 +16,6 @@ from rocmdash.prom.mock import MI300_PART, FakePrometheusHTTP, SyntheticNode
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-class _Stop(Exception):
-    pass
-
-
 def _import_our_app():
     spec = importlib.util.spec_from_file_location("rocmdash_app", os.path.join(ROOT, "app.py"))
     mod = importlib.util.module_from_spec(spec)
@@ -26,18 +23,24 @@ def _import_our_app():
     return mod
 
 
-def _run_reference(reference_app, st, node, monkeypatch, widget_values=None):
-    monkeypatch.setattr(reference_app.requests, "get", FakePrometheusHTTP(node))
+PAGE_CASES = [(False, True), (True, True), (True, False)]
 
-    def stop(_):
-        raise _Stop()
 
-    monkeypatch.setattr(reference_app.time, "sleep", stop)
-    st.reset()
-    st.WIDGET_VALUES.update(widget_values or {})
-    with pytest.raises(_Stop):
-        reference_app.main()
-    return list(st.CALLS)
+def page_case(select_all, gauge):
+    """(node, widget values) of a page case: the recorder's input and the tests'."""
+    node = SyntheticNode(8, card_model=MI300_PART, seed=11)
+    node.overrides[("3", "amd_gpu_average_package_power")] = 0  # idle GPU: excluded from power mean
+    widgets = {"Use Gauge Visualization": gauge}
+    if select_all:
+        widgets.update({f"gpu_checkbox_{g}": True for g in range(8)})
+    return node, widgets
+
+
+def _reference_calls(reference_golden, select_all, gauge):
+    """The reference's recorded Streamlit calls for a page case."""
+    from _golden import decode_calls
+
+    return decode_calls(reference_golden["page"][f"{int(select_all)}-{int(gauge)}"])
 
 
 def _run_ours(st, node, monkeypatch, widget_values=None):
@@ -84,14 +87,10 @@ def _compare(ref_calls, our_calls):
     assert rt[:14] == ot[:14] == "Last updated: "
 
 
-@pytest.mark.parametrize("select_all,gauge", [(False, True), (True, True), (True, False)])
-def test_page_matches_reference(reference_app, st_stub, monkeypatch, select_all, gauge):
-    node = SyntheticNode(8, card_model=MI300_PART, seed=11)
-    node.overrides[("3", "amd_gpu_average_package_power")] = 0  # idle GPU: excluded from power mean
-    widgets = {"Use Gauge Visualization": gauge}
-    if select_all:
-        widgets.update({f"gpu_checkbox_{g}": True for g in range(8)})
-    ref = _run_reference(reference_app, st_stub, node, monkeypatch, widgets)
+@pytest.mark.parametrize("select_all,gauge", PAGE_CASES)
+def test_page_matches_reference(reference_golden, st_stub, monkeypatch, select_all, gauge):
+    node, widgets = page_case(select_all, gauge)
+    ref = _reference_calls(reference_golden, select_all, gauge)
     ours = _run_ours(st_stub, node, monkeypatch, widgets)
     _compare(ref, ours)
     n_sel = 8 if select_all else 1

@@ -85,7 +85,7 @@ def test_no_launcher_starts_n_ranks():
     """``--gpus N`` without torch.distributed.run: the bench starts the N rank processes
     itself and the line reports N ranks, each with its own record."""
     d, err = _run([sys.executable, "bench.py", "--gpus", "4", "--cpu", "--steps", "20", "--warmup", "2", "--window",
-                   "256", "--timing-steps", "0", "--e2e-s", "1"])
+                   "256", "--full", "--timing-steps", "0", "--e2e-s", "1"])
     assert d["n_gpus"] == 4 and len(d["ranks"]) == 4, d
     assert sorted(r["rank"] for r in d["ranks"]) == [0, 1, 2, 3]
     assert "started 4 rank processes" in err
@@ -142,3 +142,25 @@ def test_node_window_tail_and_mode_label():
     assert bench._node_window_mode(N, L) == "distributed radix select"
     N.long = False
     assert bench._node_window_mode(N, None) == "sorted windows all-gathered + rank selection"
+
+
+def test_plain_run_and_dump_outputs(tmp_path):
+    """A plain run has no side measurement in it and refuses one asked for without
+    ``--full``; ``--dump-outputs`` writes the same arrays from run to run (seeded rows
+    through the timed path), whatever the live rows of the timed region were."""
+    import numpy as np
+
+    res = _rc([sys.executable, "bench.py", *ARGS, "--e2e-s", "1"])
+    assert res.returncode == 2 and "needs --full" in res.stderr and not res.stdout.strip(), res.stderr[-2000:]
+    dumps = []
+    for name, sampling in (("a", "free"), ("b", "closed")):
+        d, _ = _run([sys.executable, "bench.py", *ARGS, "--sampling", sampling, "--dump-outputs", str(tmp_path / name)])
+        assert d["full"] is False and d["steps"] == 5 and d["ms_per_step"] > 0
+        assert d["deployed_path"] is None and d["device_us_p50"] is None and "production_node" not in d
+        assert d["dumped_outputs"]["node_stats"] == [1, 16, 8]
+        dumps.append({f: np.load(tmp_path / name / f"{f}.npy") for f in d["dumped_outputs"]})
+    a, b = dumps
+    assert a["node_stats"].dtype == np.float32 and a["frame_numbers"].dtype == np.float64
+    assert a["node_stats"][0, :, 7].tolist() == [256.0] * 16  # every window full of the seeded rows
+    for f in a:
+        np.testing.assert_array_equal(a[f], b[f])

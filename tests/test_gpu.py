@@ -401,7 +401,7 @@ def test_bench_contract_gpu(gather):
     real (native) RCCL all-gather and the publish kernel, validated bit for bit; and
     the deployed path's page refresh and display age."""
     res = subprocess.run(
-        [sys.executable, "bench.py", "--steps", "200", "--warmup", "20", "--gather", gather, "--timing-steps", "50",
+        [sys.executable, "bench.py", "--steps", "200", "--warmup", "20", "--gather", gather, "--full", "--timing-steps", "50",
          "--e2e-s", "3"],
         cwd=ROOT, capture_output=True, text=True, timeout=600,
     )

@@ -69,7 +69,7 @@ def test_bench_multirank_one_gpu():
     timed region on the validated native gather, the side run's HIP events, the deployed
     path run by both ranks; the line says it is a rehearsal, not a 2-GPU number."""
     res = subprocess.run(_torchrun(2, "bench.py", "--gpus", "2", "--steps", "100", "--warmup", "10", "--source",
-                                   "synthetic", "--counters", "synthetic", "--timing-steps", "20", "--e2e-s", "2"),
+                                   "synthetic", "--counters", "synthetic", "--full", "--timing-steps", "20", "--e2e-s", "2"),
                          cwd=ROOT, capture_output=True, text=True, timeout=300, env=_env())
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert res.returncode == 0 and len(lines) == 1, (res.stdout[-3000:], res.stderr[-4000:])
@@ -122,7 +122,7 @@ def test_bench_self_launches_ranks_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     res = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "100", "--warmup", "10", "--source",
-                          "synthetic", "--counters", "synthetic", "--timing-steps", "20", "--e2e-s", "1"],
+                          "synthetic", "--counters", "synthetic", "--full", "--timing-steps", "20", "--e2e-s", "1"],
                          cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert res.returncode == 0 and len(lines) == 1, (res.stdout[-3000:], res.stderr[-4000:])
@@ -144,7 +144,7 @@ def test_bench_eight_ranks_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     res = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--steps", "50", "--warmup", "5", "--source",
-                          "synthetic", "--counters", "synthetic", "--timing-steps", "10", "--e2e-s", "1"],
+                          "synthetic", "--counters", "synthetic", "--full", "--timing-steps", "10", "--e2e-s", "1"],
                          cwd=ROOT, capture_output=True, text=True, timeout=420, env=env)
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert res.returncode == 0 and len(lines) == 1, (res.stdout[-3000:], res.stderr[-4000:])
@@ -165,7 +165,7 @@ def test_bench_slow_ranks_restart_alone_one_gpu():
         env.pop(k, None)
     env["ROCMDASH_BENCH_FAKE_SLOW"] = "1:0,3:0"
     res = subprocess.run([sys.executable, "bench.py", "--gpus", "4", "--steps", "50", "--warmup", "5", "--source",
-                          "synthetic", "--counters", "synthetic", "--timing-steps", "10", "--e2e-s", "0"],
+                          "synthetic", "--counters", "synthetic", "--full", "--timing-steps", "10", "--e2e-s", "0"],
                          cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert res.returncode == 0 and len(lines) == 1, (res.stdout[-3000:], res.stderr[-4000:])

@@ -138,7 +138,7 @@ def test_bench_cpu_torchrun(world):
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr",
            "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", str(world), "--steps", "20", "--warmup", "2",
-           "--cpu", "--window", "256", "--e2e-s", "2"]
+           "--cpu", "--window", "256", "--full", "--e2e-s", "2"]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

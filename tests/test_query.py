@@ -1,5 +1,6 @@
 """Query layer: reference contract of fetch_gpu_metrics (app.py:153-227), its edge
-cases and behavioural parity with the reference itself."""
+cases and behavioural parity with the reference itself (its
+recorded behaviour on the same data: tests/golden/, tests/_golden.py)."""
 
 import math
 
@@ -15,20 +16,11 @@ def _client(node, **kw):
     return q.PrometheusClient(endpoint="http://prom:9090/api/v1/query", get=FakePrometheusHTTP(node, **kw))
 
 
-def test_promql_strings_match_reference_bytes(reference_app, monkeypatch):
-    # The reference builds both strings inline (app.py:157, 167-172); check ours by
-    # capturing what the reference sends through a patched requests.get.
-    sent = []
-    node = SyntheticNode(2, host_ip="10.1.2.3")
-    fake = FakePrometheusHTTP(node)
-
-    def get(url=None, params=None, **kw):
-        sent.append(params["query"])
-        return fake(url=url, params=params)
-
-    monkeypatch.setattr(reference_app.requests, "get", get)
-    reference_app.fetch_gpu_metrics()
-    assert sent[0] == q.node_discovery_query(reference_app.PROMETHEUS_METRICS_PODNAME)
+def test_promql_strings_match_reference_bytes(reference_golden):
+    # The reference builds both strings inline (app.py:157, 167-172); check ours against
+    # what the reference sent through a patched requests.get (node host_ip 10.1.2.3).
+    sent = reference_golden["queries_sent"]
+    assert sent[0] == q.node_discovery_query(reference_golden["podname"])
     assert sent[1] == q.gpu_metrics_query("10.1.2.3")
 
 
@@ -49,22 +41,23 @@ def test_fetch_contract_shapes_and_dtypes():
     assert "vram_usage_ratio" in stats["mean"].index and "card_model" not in stats["mean"].index
 
 
-def test_parity_with_reference_on_same_data(reference_app, monkeypatch):
-    node = SyntheticNode(8, seed=3)
-    fake = FakePrometheusHTTP(node)
-    monkeypatch.setattr(reference_app.requests, "get", fake)
-    ref_df, ref_stats = reference_app.fetch_gpu_metrics()
+def test_parity_with_reference_on_same_data(reference_golden):
+    from _golden import decode
+
+    node = SyntheticNode(8, seed=3)  # the recorded fetch ran on this node
+    ref = reference_golden["fetch"]
     df, stats = q.fetch_gpu_metrics(_client(node))
-    assert list(df.index) == list(ref_df.index)
-    assert list(df.columns) == list(ref_df.columns)
+    assert list(df.index) == ref["index"]
+    assert list(df.columns) == ref["columns"]
     for c in df.columns:
         if c == "card_model":
-            assert list(df[c]) == list(ref_df[c])
+            assert list(df[c]) == ref["card_model"]
         else:
-            np.testing.assert_allclose(df[c].astype(float), ref_df[c].astype(float))
+            np.testing.assert_allclose(df[c].astype(float), ref["numeric"][c])
     for k in ("mean", "max", "min"):
-        pd.testing.assert_index_equal(stats[k].index, ref_stats[k].index)
-        np.testing.assert_allclose(stats[k].astype(float), ref_stats[k].astype(float))
+        ref_stat = decode(ref["stats"][k])
+        pd.testing.assert_index_equal(stats[k].index, ref_stat.index)
+        np.testing.assert_allclose(stats[k].astype(float), ref_stat.astype(float))
 
 
 def test_lexicographic_index_like_pivot():
@@ -73,8 +66,11 @@ def test_lexicographic_index_like_pivot():
     assert list(df.index) == ["0", "1", "10", "2"]
 
 
-@pytest.mark.parametrize("fault", ["duplicate", "missing_total", "http500", "no_pod", "bad_json"])
-def test_error_paths_return_none_and_report(fault, reference_app, monkeypatch):
+FAULTS = ["duplicate", "missing_total", "http500", "no_pod", "bad_json"]
+
+
+def fault_case(fault):
+    """(node, FakePrometheusHTTP keywords) of a fault: the recorder's input and the tests'."""
     node = SyntheticNode(2)
     kw = {}
     if fault == "duplicate":
@@ -88,13 +84,18 @@ def test_error_paths_return_none_and_report(fault, reference_app, monkeypatch):
         node.pod = "something-else"
     elif fault == "bad_json":
         kw = {"body": "<html>oops</html>"}
+    return node, kw
+
+
+@pytest.mark.parametrize("fault", FAULTS)
+def test_error_paths_return_none_and_report(fault, reference_golden):
+    node, kw = fault_case(fault)
     errors = []
     df, stats = q.fetch_gpu_metrics(_client(node, **kw), on_error=errors.append)
     assert df is None and stats is None
     assert len(errors) == 1 and errors[0].startswith("Error fetching GPU metrics: ")
-    # the reference takes the error path on the same input too
-    monkeypatch.setattr(reference_app.requests, "get", FakePrometheusHTTP(node, **kw))
-    assert reference_app.fetch_gpu_metrics() == (None, None)
+    # the reference took the error path on the same input too
+    assert tuple(reference_golden["faults"][fault]) == (None, None)
 
 
 def test_partial_metric_missing_for_one_gpu_is_nan():

@@ -70,7 +70,7 @@ for s in "$@"; do
         > "$OUT/pytest_gpu.log" 2>&1 || fail "$OUT/pytest_gpu.log"
       tail -3 "$OUT/pytest_gpu.log" ;;
     bench)
-      timeout -k 10 240 python3 bench.py --steps 20 --warmup 5 --json-out "$OUT/bench_k20.json" \
+      timeout -k 10 240 python3 bench.py --steps 20 --warmup 5 --full --json-out "$OUT/bench_k20.json" \
         > "$OUT/bench_k20.log" 2>&1 || fail "$OUT/bench_k20.log"
       tail -c 300 "$OUT/bench_k20.json" ;;
     ab)
@@ -108,7 +108,7 @@ for s in "$@"; do
         grep p50_us "$OUT/kernarg_$kd.log" | cut -c1-150
       done ;;
     nodewin)
-      timeout -k 10 300 python3 bench.py --window 16777216 --node-window --gather rccl --steps 20 --warmup 3 \
+      timeout -k 10 300 python3 bench.py --full --window 16777216 --node-window --gather rccl --steps 20 --warmup 3 \
         --timing-steps 0 --e2e-s 0 --prefill 2000 --prefill-generated 16777216 --json-out "$OUT/bench_nodewin_2p24.json" \
         > "$OUT/bench_nodewin_2p24.log" 2>&1 || fail "$OUT/bench_nodewin_2p24.log"
       tail -c 600 "$OUT/bench_nodewin_2p24.json" ;;

@@ -23,7 +23,7 @@ rc=$?; grep -v amdgpu.ids "$OUT/smoke.log" | tail -4; [[ $rc == 0 ]] || exit $rc
 for cfg in "bench_n1|" "bench_n1_2|" "bench_n1_3|" "bench_n1_extended|--extended" "bench_n1_closed|--sampling closed" "bench_n1_serial|--sampling closed --prefetch 0" "bench_n1_rccl|--gather rccl"; do
   name=${cfg%%|*}; args=${cfg#*|}
   step "bench $name $args"
-  timeout -k 10 300 python3 bench.py $args --json-out "$OUT/$name.json" > "$OUT/$name.log" 2>&1
+  timeout -k 10 300 python3 bench.py --full $args --json-out "$OUT/$name.json" > "$OUT/$name.log" 2>&1
   rc=$?; tail -1 "$OUT/$name.log" | cut -c1-160; [[ $rc == 0 ]] || exit $rc
 done
 step "rocprofv3 kernel trace of the headline bench (device counters off under the profiler)"
