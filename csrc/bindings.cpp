@@ -243,6 +243,41 @@ PYBIND11_MODULE(_native, m) {
         "per ring (rows per workgroup, workgroups per segment) of the long-window passes");
   m.def("long_window_node_cap", &long_window_node_cap, py::arg("maxmid"), py::arg("nranks"),
         "node bracket records: the next refresh's key cap from the node's most kept keys");
+  // for the CPU tests only (tests/test_lw_worklist.py): the incremental pass B's work list and
+  // its shaping as LongWindowSet computes them; not an interface of the service
+  m.attr("LONG_WINDOW_NEVER") = kLongNever;
+  m.def(
+      "long_window_work_list",
+      [](uint32_t window, const std::vector<std::array<uint64_t, 4>>& rings, std::vector<uint64_t> seg_head,
+         const std::vector<uint32_t>& want, const std::vector<uint32_t>& changed) {
+        std::vector<LwWorkRing> rs;
+        size_t series = 0, segs = 0;
+        for (const auto& r : rings) {
+          if (r[0] == 0 || r[0] > uint64_t(kLongMaxWidth) || r[1] == 0 || r[2] == 0)
+            throw std::invalid_argument("long_window_work_list: rings are (width 1..16, chunk_rows, nchunks, copied)");
+          rs.push_back(LwWorkRing{uint32_t(r[0]), uint32_t(r[1]), uint32_t(r[2]), r[3]});
+          series += r[0];
+          segs += (r[0] + 7) / 8;
+        }
+        if (window == 0 || (window & (window - 1)) || seg_head.size() < segs || want.size() != series ||
+            changed.size() != series)
+          throw std::invalid_argument("long_window_work_list: a power-of-two window, a head per segment, flags per series");
+        auto work = long_window_work_list(window, rs.data(), rs.size(), seg_head.data(), want.data(), changed.data());
+        return py::make_tuple(work, seg_head);
+      },
+      py::arg("window"), py::arg("rings"), py::arg("seg_head"), py::arg("want"), py::arg("changed"),
+      "test hook: (the (segment << 20 | chunk) list pass B streams, the updated segment heads)");
+  m.def(
+      "long_window_shape_work",
+      [](const std::vector<uint32_t>& work, const std::vector<uint32_t>& seg_cols, uint32_t flat_grid,
+         uint32_t fuse_chunks, size_t split_max, bool fuse) {
+        for (uint32_t e : work)
+          if ((e >> 20) >= seg_cols.size()) throw std::invalid_argument("long_window_shape_work: segment out of range");
+        const LwWorkShape sh = long_window_shape_work(work, seg_cols, flat_grid, fuse_chunks, split_max, fuse);
+        return py::make_tuple(sh.pass, sh.fused, sh.colsplit, sh.grid);
+      },
+      py::arg("work"), py::arg("seg_cols"), py::arg("flat_grid"), py::arg("fuse_chunks"), py::arg("split_max"),
+      py::arg("fuse"), "test hook: (pass B's list, the fused list, colsplit, pass B's grid)");
   py::class_<LongWindowSet, std::shared_ptr<LongWindowSet>>(m, "LongWindowSet")
       .def(py::init<uint32_t, int, bool, uint32_t>(), py::arg("window"), py::arg("device"), py::arg("use_graph") = false,
            py::arg("chunk_rows") = 0)

@@ -22,7 +22,7 @@
 //           skips the whole stream). The prefix (+ the bits no sample varies in) IS
 //           the key of the sample at that rank. The last scan writes [S, 8].
 //
-// Bracket mode (default; long_window.hip "Bracket mode"): in front of the chain, pass B
+// Bracket mode (default; long_window_brackets.hip "Bracket mode"): in front of the chain, pass B
 // streams the window once, counting per percentile the samples below and inside a
 // bracket around the previous refresh's percentile key and keeping the keys inside; scan
 // B selects the percentiles among those keys when every one fell inside its bracket, and
@@ -49,6 +49,7 @@
 #include <utility>
 #include <vector>
 
+#include "long_window_buffers.h"
 #include "ring.h"
 
 namespace rocmdash {
@@ -106,6 +107,39 @@ std::vector<std::pair<uint32_t, uint32_t>> long_window_chunk_plan(uint32_t windo
 // this refresh's node-wide most kept keys - lw_node_cap_next (rocmdash.runtime.lw_brackets
 // node_cap_next mirrors it)
 uint32_t long_window_node_cap(uint32_t maxmid, uint32_t nranks);
+
+// ---- the incremental pass B's work, as pure functions of a few integers and host flags
+// (LongWindowSet only copies and launches what they return). Exposed to Python for the
+// CPU tests alone (tests/test_lw_worklist.py): not an interface of the service. ----
+constexpr uint64_t kLongNever = ~0ull;  // a segment head: the segment never had a pass B
+struct LwWorkRing {
+  uint32_t width;       // series of the ring: ceil(width / 8) segments of <= 8 columns
+  uint32_t chunk_rows;  // rows per chunk (chunks are the device ring's slots, long_window_pass.h)
+  uint32_t nchunks;
+  uint64_t copied;      // the ring head the device window holds
+};
+// The (segment, chunk) list pass B has to stream, seg << 20 | chunk, segments in ring order:
+// per segment, every chunk when one of its series' brackets changed since the segment's
+// last pass B (or it never had one, or a window or more entered), else only the chunks the
+// rows that entered since then landed in (wrapping: the tail's chunks, then the head's).
+// A segment none of whose series wants brackets gets none, and its head becomes
+// kLongNever (its counts go stale). seg_head [segments]: the ring head at each segment's
+// last pass B, updated in place. want / changed: per series, non-zero = set.
+std::vector<uint32_t> long_window_work_list(uint32_t window, const LwWorkRing* rings, size_t nrings,
+                                            uint64_t* seg_head, const uint32_t* want, const uint32_t* changed);
+struct LwWorkShape {
+  std::vector<uint32_t> pass;   // pass B's list (empty with grid == flat_grid: every chunk, no list)
+  std::vector<uint32_t> fused;  // the chunks scan B streams itself (seg << 20 | chunk)
+  bool colsplit = false;        // pass: seg << 23 | column << 20 | chunk, one entry per column
+  uint32_t grid = 0;            // pass B's workgroups (0: no pass B launch)
+};
+// Pass B's grid from the work list. A list as long as the flat grid: the flat grid. With
+// fuse, segments with at most fuse_chunks entries go to the fused list. What is left is
+// split by column when that makes at most split_max workgroups and fits the flat grid. An
+// empty list without fuse still runs one workgroup (entry 0): the grid's first workgroup
+// copies the brackets scan B decides with. seg_cols: columns per segment.
+LwWorkShape long_window_shape_work(std::vector<uint32_t> work, const std::vector<uint32_t>& seg_cols,
+                                   uint32_t flat_grid, uint32_t fuse_chunks, size_t split_max, bool fuse);
 
 class LongWindowSet {
  public:
@@ -252,7 +286,7 @@ class LongWindowSet {
  private:
   struct RingState {
     std::shared_ptr<SeriesRing> ring;
-    float* dev = nullptr;  // [W][width]: row r at slot r & (W - 1)
+    LwDeviceBuf dev;       // float [W][width]: row r at slot r & (W - 1)
     uint64_t copied = 0;   // rows [0, copied) are on the device (or were lost)
     uint64_t last_head = 0;  // the ring head at the previous refresh
     uint32_t first_series = 0;
@@ -274,16 +308,35 @@ class LongWindowSet {
   bool ingest_pending_ = false;
   static constexpr size_t kIngestMaxBytes = 256 << 10;  // larger stagings (a fill) take the DMA copies
   std::vector<std::array<uint64_t, 3>> ingest_segs_;  // (ring, first row, rows) to ingest
-  void* host_params_dev_ = nullptr;  // host_params_ as the device sees it
-  uint32_t* work_host_dev_ = nullptr;  // work_host_ as the device sees it
-  LwArgs make_args(float* out, int mode) const;
+  void finish_stage(hipStream_t stream);  // flush_stage without a work list + the slot's event
+  // brk: the refresh launches pass B + scan B; incr: ... incrementally
+  LwArgs make_args(float* out, int mode, bool brk, bool incr) const;
   size_t lds_bytes(int pass) const;
   void check_args(const LwArgs& a) const;
-  void enqueue_chain(hipStream_t stream, const LwArgs& a);
-  void enqueue_passes(hipStream_t stream, float* out);
+  // what the node refresh enqueues between the chain's kernels (none: the local chain)
+  struct ChainHooks {
+    std::function<void()> before_pass0;   // lw_node_predict + the predictions' all-gather
+    std::function<void()> after_pass0;    // lw_node_partials + their all-gather, pass 0's all-reduce
+    std::function<void(int)> after_pass;  // pass k = 1..3's all-reduce
+  };
+  void enqueue_chain(hipStream_t stream, const LwArgs& a, const ChainHooks& hooks = {});
+  void enqueue_passes(hipStream_t stream, float* out, bool brk);
   void allocate_mode(int mode);
-  std::vector<uint32_t> work_list(int mode);
-  uint32_t upload_work(hipStream_t stream, LwArgs& a, int mode, uint32_t slot, bool fuse = false);
+  // upload the work list, pass B, the resolve kernels, then wait for the report: the one
+  // bracket step of the local and the node refresh. resolve(fused) enqueues the mode's scan
+  // B (and counts its launches); returns the series left to the radix chain.
+  struct BracketStep {
+    int mode;
+    bool fuse;         // short segments may go to scan B's own workgroups
+    bool host_times;   // account host_enqueue_ns / host_wait_ns
+    double timeout_s;
+    const std::function<bool()>* abandon;
+    uint32_t* maxmid;  // out (may be null): the node select's most kept keys
+  };
+  uint32_t bracket_step(hipStream_t stream, LwArgs& a, const BracketStep& step,
+                        const std::function<void(bool)>& resolve);
+  // returns pass B's grid; *fused: scan B streams a part of the list itself
+  uint32_t upload_work(hipStream_t stream, LwArgs& a, int mode, uint32_t slot, bool fuse, bool* fused);
   static constexpr uint32_t kFuseChunks = 4;  // fused pass B: at most this many changed chunks per segment
   static constexpr size_t kSplitMax = 2048;  // column-split pass B: at most this many workgroups
   uint32_t wait_report(int mode, uint32_t seq, double timeout_s, uint32_t* maxmid = nullptr,
@@ -300,33 +353,31 @@ class LongWindowSet {
   // (profiles/r05/lw_rounds/, lw_incr_v4/)
   uint32_t plan_rounds_ = 3;
   uint32_t brk_target_ = 2048;
-  unsigned long long* dbg_ = nullptr;
+  LwDeviceBuf dbg_;  // unsigned long long [S][kBrkQ][8]: scan B's phase clocks (set_phase_clocks)
   uint32_t nseries_ = 0;
   uint32_t max_chunks_ = 0;  // the most chunks of any ring (partials / slab-count stride)
   uint32_t cand_cap_ = 0;    // candidate slots per series (>= every ring's chunks x rows)
   uint32_t pass_wgs_ = 0;    // the flat pass grid: every segment's chunks
+  std::vector<uint32_t> seg_cols_;  // columns per segment, in segment order (plan_chunks)
   std::vector<RingState> rings_;
   // work buffers (allocated at the first refresh, when every ring is known)
-  void* params_ = nullptr;      // device LwParams
-  void* part_ = nullptr;        // per (series, chunk) partials
-  uint32_t* hist0_ = nullptr;   // [S][1024]
-  uint32_t* dig0_ = nullptr;    // [S][3]: pass 0's digit shift, reference key, width
-  uint32_t* histk_ = nullptr;   // [S][6][256]
-  void* sel_ = nullptr;         // per series: ranks, residuals, prefixes
-  void* host_params_ = nullptr;  // pinned staging slots for the parameter copy
-  std::vector<hipEvent_t> slot_done_;
+  LwDeviceBuf params_;  // LwParams
+  LwDeviceBuf part_;    // LwPartial per (series, chunk)
+  LwDeviceBuf hist0_;   // uint32 [S][1024]
+  LwDeviceBuf dig0_;    // uint32 [S][3]: pass 0's digit shift, reference key, width
+  LwDeviceBuf histk_;   // uint32 [S][6][256]
+  LwDeviceBuf sel_;     // LwSel per series: ranks, residuals, prefixes
+  LwHostBuf host_params_;  // pinned staging slots for the parameter copy
+  std::vector<LwEvent> slot_done_;
   uint32_t slot_ = 0;
-  hipStream_t cap_stream_ = nullptr;
-  hipGraph_t graph_ = nullptr;
-  hipGraphExec_t exec_ = nullptr;
+  LwStream cap_stream_;
+  LwGraph graph_;
+  LwGraphExec exec_;
   float* graph_out_ = nullptr;
   // node mode (refresh_node): predictions and partials, this rank's and all-gathered
-  void* pred_local_ = nullptr;
-  void* pred_all_ = nullptr;
-  void* agg_local_ = nullptr;
-  void* agg_all_ = nullptr;
-  void* nbl_ = nullptr;    // node bracket mode: this rank's records [S]
-  void* nball_ = nullptr;  // ... every rank's [nranks][S]
+  LwDeviceBuf pred_local_, pred_all_, agg_local_, agg_all_;
+  LwDeviceBuf nbl_;    // node bracket mode: this rank's records [S]
+  LwDeviceBuf nball_;  // ... every rank's [nranks][S]
   uint32_t node_maxmid_ = 0;
   uint32_t node_cap_ = 1024;  // the records' key cap this refresh (lw_node_cap_next; kNodeCap until measured)
   bool node_timed_[6] = {false, false, false, false, false, false};
@@ -339,38 +390,35 @@ class LongWindowSet {
   bool brackets_ = true;
   bool incremental_ = true;
   bool fuse_ = true;
-  static constexpr uint64_t kNever = ~0ull;
+  static constexpr uint64_t kNever = kLongNever;
   // one bracket state per kind of refresh: 0 = local (refresh), 1 = node (refresh_node)
   struct BrkMode {
-    void* brk = nullptr;       // [S] brackets (persist across refreshes)
-    void* brk_used = nullptr;  // [S] the brackets the current refresh's pass B used
-    void* bpart = nullptr;     // [S][chunks] pass B's per-chunk bracket counts
-    uint32_t* bcand = nullptr;  // pass B's kept keys (LwRing::boff / bstride)
-    uint32_t* hflags = nullptr;  // [S] pinned host: series that want brackets (kernels write)
-    uint32_t* hflags_dev = nullptr;
-    uint32_t* bchg = nullptr;  // [S] pinned host: the series' brackets moved (kernels write, host clears)
-    uint32_t* bchg_dev = nullptr;
-    unsigned long long* report = nullptr;  // pinned host: {seq, series left to the chain, node's most kept keys}
-    unsigned long long* report_dev = nullptr;
-    uint32_t* brk_cnt = nullptr;  // device: scan B's finished workgroups (lw_brk_finish)
+    LwDeviceBuf brk;       // LwBrk [S] brackets (persist across refreshes)
+    LwDeviceBuf brk_used;  // LwBrk [S] the brackets the current refresh's pass B used
+    LwDeviceBuf bpart;     // LwBrkPart [S][chunks] pass B's per-chunk bracket counts
+    LwDeviceBuf bcand;     // uint32: pass B's kept keys (LwRing::boff / bstride)
+    LwHostBuf hflags;      // uint32 [S] pinned host: series that want brackets (kernels write)
+    LwHostBuf bchg;        // uint32 [S] pinned host: the series' brackets moved (kernels write, host clears)
+    LwHostBuf report;      // one 64-bit word, pinned host: {seq, series left to the chain, node's most kept keys}
+    LwDeviceBuf brk_cnt;   // uint32 [2]: scan B's finished workgroups (lw_brk_finish)
     std::vector<uint64_t> seg_head;  // per segment: the ring head at its last pass B (kNever: none)
-    hipEvent_t done = nullptr;       // the mode's last refresh
+    LwEvent done;                    // the mode's last refresh
   };
   BrkMode bm_[2];
-  bool brk_now_ = false;   // this refresh launches pass B + scan B
-  bool incr_now_ = false;  // ... incrementally
   uint64_t bcand_keys_ = 0;  // kept-key slots of one mode (every series)
-  uint32_t* work_dev_ = nullptr;   // incremental pass B's work list
-  uint32_t* work_host_ = nullptr;  // pinned staging, one list per parameter slot
+  LwDeviceBuf work_dev_;     // uint32: incremental pass B's work list
+  LwHostBuf work_host_;      // uint32: pinned staging, one list per parameter slot
   uint32_t seq_ = 0;               // refreshes staged (the report word's number)
   uint32_t cur_slot_ = 0;          // the parameter slot of the refresh being enqueued
-  hipEvent_t last_done_ = nullptr;  // after this set's last enqueued kernel (destructor waits on it)
-  uint32_t* cand_ = nullptr;    // [S][W] candidate keys (compaction)
-  uint32_t* cand_n_ = nullptr;  // [S][chunks] keys per pass-2 workgroup slab
+  LwDeviceBuf cand_;    // uint32 [S][W] candidate keys (compaction)
+  LwDeviceBuf cand_n_;  // uint32 [S][chunks] keys per pass-2 workgroup slab
   bool exec_stale_ = false;  // the captured graph predates a setting change
-  std::vector<hipEvent_t> node_events_;
+  std::vector<LwEvent> node_events_;
   bool timed_ = false;
   LongWindowStats st_;
+  // after this set's last enqueued kernel: the destructor waits on it, then the members
+  // release in reverse order - this event first, the buffers after it
+  LwEvent last_done_;
 };
 
 }  // namespace rocmdash

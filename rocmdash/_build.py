@@ -29,6 +29,8 @@ ARCH = os.environ.get("ROCMDASH_OFFLOAD_ARCH", "gfx950")
 SOURCES = [
     "window_stats.hip",
     "long_window.hip",
+    "long_window_radix.hip",
+    "long_window_brackets.hip",
     "node_window.hip",
     "calib.hip",
     "publish.hip",

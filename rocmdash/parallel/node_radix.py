@@ -43,7 +43,7 @@ NO_PRED = (0, 0xFFFFFFFF, 0)  # (pmin, pmax, lo): the top-byte fallback
 
 
 def fkey(x: np.ndarray) -> np.ndarray:
-    """Order-preserving float32 -> uint32 key (as csrc/long_window.hip ``fkey``)."""
+    """Order-preserving float32 -> uint32 key (as csrc/long_window_dev.h ``fkey``)."""
     u = np.asarray(x, np.float32).view(np.uint32).astype(np.uint64)
     return np.where(u & 0x80000000, (~u) & 0xFFFFFFFF, u | 0x80000000).astype(np.uint64)
 

@@ -1,5 +1,5 @@
 """Bracket mode of the long-window statistics: the host model of ``lw_pass_brk`` +
-``lw_scan_brk`` (csrc/long_window.hip "Bracket mode").
+``lw_scan_brk`` (csrc/long_window_brackets.hip "Bracket mode").
 
 A window of W samples per series changes by the few rows that entered and left since the
 previous refresh, so each percentile moves by a few ranks. The previous refresh's
@@ -51,7 +51,7 @@ PCT = (50.0, 90.0, 99.0)
 
 
 def fkey(x: np.ndarray) -> np.ndarray:
-    """Order-preserving float32 -> uint32 key (csrc/long_window.hip ``fkey``)."""
+    """Order-preserving float32 -> uint32 key (csrc/long_window_dev.h ``fkey``)."""
     u = np.asarray(x, np.float32).view(np.uint32).astype(np.uint64)
     return np.where(u & 0x80000000, (~u) & 0xFFFFFFFF, u | 0x80000000).astype(np.uint64)
 
@@ -276,7 +276,7 @@ def node_cap_next(maxmid: int, nranks: int) -> int:
 
 @dataclass
 class NodeBracketModel(BracketModel):
-    """Node bracket mode (csrc/long_window.hip ``lw_node_brk_local`` + ``lw_node_brk_select``,
+    """Node bracket mode (csrc/long_window_brackets.hip ``lw_node_brk_local`` + ``lw_node_brk_select``,
     host ``LongWindowSet::refresh_node``): the node's brackets - the same on every rank -
     are counted against each rank's own window; ONE all-gather of every rank's record
     (partials, below / inside counts, kept keys up to ``NODE_CAP``, rows entered) lets

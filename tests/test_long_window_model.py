@@ -1,4 +1,4 @@
-"""CPU model of the long-window kernel's adaptive digit schedule (csrc/long_window.hip).
+"""CPU model of the long-window kernel's adaptive digit schedule (csrc/long_window_radix.hip).
 
 The kernel resolves only the key bits that vary over the window: pass 0 histograms a
 digit of 8 or 10 bits just below the top bit of a PREDICTED range (a superset of the true

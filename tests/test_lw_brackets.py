@@ -218,7 +218,7 @@ def test_node_brackets_exact_and_hit(nranks, shape):
 
 
 def test_node_cap_next():
-    """The record cap mirrors csrc/long_window.hip lw_node_cap_next: 64-key steps, a floor
+    """The record cap mirrors csrc/long_window_args.h lw_node_cap_next: 64-key steps, a floor
     of 4x a rank's share of the node target, 2x headroom, at most kNodeCap."""
     from rocmdash.runtime.lw_brackets import NODE_CAP, node_cap_next
 

@@ -80,7 +80,7 @@ def rows_for(rank: int, step: int, k: int, t0: int, grid=None):
 
 
 def fkey(v: float) -> int:
-    """csrc/long_window.hip fkey: the order-preserving uint32 key of a float32."""
+    """csrc/long_window_dev.h fkey: the order-preserving uint32 key of a float32."""
     import numpy as np
 
     u = int(np.array([v], np.float32).view(np.uint32)[0])
