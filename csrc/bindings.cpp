@@ -473,7 +473,7 @@ PYBIND11_MODULE(_native, m) {
         args.pct[1] = p1;
         args.pct[2] = p2;
         args.num_rings = 1;
-        RingDesc& r = args.rings[0];
+        RingHead& r = args.rings[0].h;
         for (size_t j = 0; j < cols.size(); ++j) {
           if (cols[j] >= stride) throw std::invalid_argument("column must be < stride");
           if (cols[j] != cols[0] + j) throw std::invalid_argument("columns must be one ascending run");
@@ -498,6 +498,37 @@ PYBIND11_MODULE(_native, m) {
       py::arg("base_ptr"), py::arg("head"), py::arg("stride"), py::arg("mask"), py::arg("n"), py::arg("cols"),
       py::arg("out_ptr"), py::arg("stream"), py::arg("p0") = 50.f, py::arg("p1") = 90.f, py::arg("p2") = 99.f);
   m.def("sort_width_for", &sort_width_for, py::arg("n"));
+  // for the CPU tests only (tests/test_window_stats_rules.py): the rules the window-stats kernel
+  // and DeviceWindowSet run (window_stats_rules.h); not an interface of the service
+  m.attr("MAX_INCREMENTAL") = int(kMaxIncremental);
+  m.def("ws_incremental_step", [](uint64_t h0, uint32_t n0, uint32_t cur, uint64_t h1, uint32_t n1, uint64_t depth,
+                                  uint32_t sorted_cap) {
+    const IncStep s = incremental_step(h0, n0, cur, h1, n1, depth, sorted_cap);
+    return py::make_tuple(s.ok, s.kadd, s.krem);
+  });
+  m.def("ws_next_half", &next_half, py::arg("incremental"), py::arg("have_state"), py::arg("cur"));
+  m.def("ws_changed_span", [](uint32_t kr, uint32_t ka, uint32_t first_leave, uint32_t last_leave, uint32_t first_ins,
+                              uint32_t last_ins, uint32_t nv) {
+    const Span s = changed_span(kr, ka, first_leave, last_leave, first_ins, last_ins, nv);
+    return py::make_tuple(s.lo, s.hi);
+  });
+  m.def("ws_one_row_map", [](uint32_t kr, uint32_t ka, uint32_t leave, uint32_t ins) {
+    const OneRowMap m = one_row_map(kr, ka, leave, ins);
+    return py::make_tuple(m.x, m.pn);
+  });
+  m.def("ws_one_row_src", [](uint32_t x, uint32_t pn, uint32_t p) { return OneRowMap{x, pn}.src(p); });
+  m.def("ws_wanted_positions", [](uint32_t nv, std::array<float, 3> pct) {
+    const double qfrac[3] = {double(pct[0]) / 100.0, double(pct[1]) / 100.0, double(pct[2]) / 100.0};
+    uint32_t idx[8];
+    float frac[3];
+    wanted_positions(nv, qfrac, idx, frac);
+    return py::make_tuple(std::vector<uint32_t>(idx, idx + 8), std::vector<float>(frac, frac + 3));
+  });
+  m.def("ws_percentile_between", &percentile_between, py::arg("x0"), py::arg("x1"), py::arg("frac"));
+  m.def("ws_launch_shape", [](uint32_t pad_pow2, bool incremental, uint32_t max_new_rows, uint32_t small_k) {
+    const LaunchShape s = launch_shape(pad_pow2, incremental, max_new_rows, small_k);
+    return py::make_tuple(s.nt, s.e);
+  });
   m.def("rccl_load", &rccl_load, py::arg("lib_path") = "",
         "Load RCCL without creating anything; returns its version code (every rank, before the init).");
   m.def(

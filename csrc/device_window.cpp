@@ -285,18 +285,13 @@ uint32_t DeviceWindowSet::refresh(float* out, void* stream_ptr, float p0, float 
     const uint64_t h = ring.head();
     const uint64_t cap_mask = ring.capacity() - 1;
     const uint32_t n = uint32_t(std::min<uint64_t>(h, W));
-    // Mirror of the kernel's path choice (window_stats.hip): the state left by the
-    // previous launch covers [last_head - last_n, last_head).
-    const bool inc = r.state_valid && h >= r.last_head && h - r.last_head <= uint64_t(kMaxIncremental) &&
-                     (h - n) >= (r.last_head - r.last_n) &&
-                     (h - n) - (r.last_head - r.last_n) <= uint64_t(kMaxIncremental) &&
-                     (r.last_head - r.last_n) + D >= h;
+    // the kernel's own path choice and half rule (window_stats_rules.h): the state left by
+    // the previous launch covers [last_head - last_n, last_head) in half r.cur
+    const bool inc = r.state_valid && incremental_step(r.last_head, r.last_n, r.cur, h, n, D, window_).ok;
     const uint64_t prev_head = r.last_head;
     const uint32_t prev_n = r.last_n;
     const uint32_t prev_cur = r.cur;
-    // the half this launch leaves current (kernel rule): the incremental path updates
-    // it in place, a full sort writes the other one
-    r.cur = r.state_valid ? (inc ? r.cur : (r.cur ^ 1u)) : 0u;
+    r.cur = next_half(inc, r.state_valid, r.cur);
     r.state_valid = true;
     r.last_head = h;
     r.last_n = n;
@@ -329,7 +324,7 @@ uint32_t DeviceWindowSet::refresh(float* out, void* stream_ptr, float p0, float 
     if (args.num_rings == uint32_t(kMaxRingsPerLaunch) || args.num_series + width > uint32_t(kMaxSeriesPerLaunch))
       flush(false);
     const uint32_t ri = args.num_rings++;
-    RingDesc& d = args.rings[ri];
+    RingHead& d = args.rings[ri].h;
     d.base = r.dev;
     d.host_rows = pull ? r.host_dev : nullptr;
     d.sorted = r.sorted;
@@ -347,7 +342,7 @@ uint32_t DeviceWindowSet::refresh(float* out, void* stream_ptr, float p0, float 
     d.n_inline = n_inline;
     for (uint32_t j = 0; j < n_inline; ++j) {  // rows h - n_inline .. h - 1 (complete: < head)
       const uint64_t row = h - n_inline + j;
-      std::memcpy(d.inl[j], ring.rows() + (row & cap_mask) * width, size_t(width) * sizeof(float));
+      std::memcpy(args.rings[ri].inl[j], ring.rows() + (row & cap_mask) * width, size_t(width) * sizeof(float));
     }
     st_.pulled_series += pull ? width : 0;
     st_.inline_rows += n_inline;

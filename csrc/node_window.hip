@@ -11,6 +11,7 @@
 
 #include "device_window.h"
 #include "window_stats.h"
+#include "window_stats_dev.h"
 
 namespace rocmdash {
 namespace {
@@ -39,26 +40,6 @@ __global__ __launch_bounds__(NT) void export_sorted_kernel(const ExportArgs a, f
   float* row = dst + size_t(blockIdx.x) * (W + 1);
   if (threadIdx.x == 0) row[0] = float(nv);
   for (uint32_t i = threadIdx.x; i < W; i += NT) row[1 + i] = i < nv ? src[i] : INFINITY;
-}
-
-__device__ inline uint32_t lower_bound(const float* a, uint32_t n, float x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__device__ inline uint32_t upper_bound(const float* a, uint32_t n, float x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a[mid] <= x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
 }
 
 // One workgroup per series. LDS = stage the N sorted lists compactly in LDS (dynamic
@@ -123,7 +104,7 @@ __global__ __launch_bounds__(NT) void node_select_kernel(const float* __restrict
       uint32_t r = j;
       for (uint32_t k = 0; k < N; ++k) {
         if (k == i) continue;
-        r += k < i ? upper_bound(list(k), cnt[k], x) : lower_bound(list(k), cnt[k], x);
+        r += k < i ? bound<true>(list(k), 0u, cnt[k], x) : bound<false>(list(k), 0u, cnt[k], x);
       }
 #pragma unroll
       for (int q = 0; q < 6; ++q)

@@ -1,7 +1,10 @@
 // Host/device interface of the CDNA4 windowed-statistics kernel (window_stats.hip).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
+
+#include "window_stats_rules.h"
 
 namespace rocmdash {
 
@@ -45,7 +48,9 @@ constexpr int kInlineRows = 4;
 constexpr int kMaxInlineWidth = 16;
 constexpr int kMaxRingsPerLaunch = 4;
 
-struct RingDesc {
+// A ring's fields before its inline rows. The kernel copies this sub-object in one go,
+// so the compiler issues every scalar load of the ring before the first use waits for any.
+struct RingHead {
   float* base;              // device pointer to row 0 of the device ring
   const float* host_rows;   // pull mode: device-mapped pinned host ring; nullptr = none
   float* sorted;            // nullptr: stateless (always a full sort); else [stride][2][sorted_cap]
@@ -64,12 +69,13 @@ struct RingDesc {
   uint32_t pred_n0;
   uint32_t pred_cur;
   uint32_t n_inline;        // rows head - n_inline .. head - 1 are in `inl`
+};
+
+struct RingDesc {
+  RingHead h;
   float inl[kInlineRows][kMaxInlineWidth];
 };
 
-// Samples that may enter (and leave) a window between two refreshes for the
-// incremental path; more than this falls back to a full sort.
-constexpr int kMaxIncremental = 256;
 constexpr int kMaxSeriesPerLaunch = 256;
 
 // Passed by value (~1.2 KiB kernel argument). The series of a launch are the columns
@@ -95,6 +101,8 @@ struct StatsArgs {
   uint64_t* tagged_out;
   RingDesc rings[kMaxRingsPerLaunch];
 };
+// the kernel argument's layout as the device sees it
+static_assert(sizeof(StatsArgs) == 1456 && offsetof(RingDesc, inl) == 88, "kernarg layout");
 
 // Launch the stats kernel for args.num_series series on `stream`; out is a device
 // pointer to [num_series][STAT_NUM] float32. `pad_pow2` is the sort width: the next
@@ -107,8 +115,5 @@ struct StatsArgs {
 // general merge prefer different widths, profiles/r02/onerow/).
 int launch_window_stats(const StatsArgs& args, uint32_t pad_pow2, float* out, void* stream, bool incremental = false,
                         uint32_t max_new_rows = ~0u);
-
-// Smallest supported sort width for a window of n samples.
-uint32_t sort_width_for(uint32_t n);
 
 }  // namespace rocmdash

@@ -51,6 +51,12 @@
 // wave-level with __shfl_xor (64 lanes), then across waves through LDS. Percentiles
 // use numpy's default 'linear' definition (tests/test_gpu.py compares against an fp64
 // PyTorch reference).
+//
+// Where the pieces live: the pure rules (path choice, half rule, changed span, one-row
+// mapping, percentile positions, LDS sizes, launch shape) in window_stats_rules.h, shared
+// with the host (device_window.cpp) and the CPU tests; the device primitives
+// (compare-exchange stages, bound searches, wave sums, the series view and its sample
+// accessor) in window_stats_dev.h; here the kernel, its two list helpers and the launch.
 
 #include <hip/hip_runtime.h>
 
@@ -60,6 +66,7 @@
 #include <cstdlib>
 
 #include "window_stats.h"
+#include "window_stats_dev.h"
 
 // Diagnostic build only (-DWS_STAMPS, tools/stamps/): s_memtime stamps by thread 0
 // of each workgroup at phase boundaries. In the real kernel no stamp executes.
@@ -84,231 +91,17 @@ namespace {
 
 constexpr int KE = kMaxIncremental / 64;  // removed/added samples per lane in the wave sorts
 
-__device__ inline uint32_t upper_bound(const float* a, uint32_t lo, uint32_t n, float x) {
-  uint32_t hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a[mid] <= x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// Ascending bitonic sort of 64*E values held E per lane, blocked layout
-// (sort index = lane * E + e); registers and cross-lane shuffles only.
-template <int E>
-__device__ inline void wave_sort(float (&a)[E], int lane) {
-#pragma unroll
-  for (uint32_t k = 2; k <= 64u * E; k <<= 1) {
-    for (uint32_t j = k >> 1; j >= uint32_t(E); j >>= 1) {
-      const int m = int(j / E);
-      const bool keep_min = ((lane & m) == 0) == (((uint32_t(lane) * E) & k) == 0);
-#pragma unroll
-      for (int e = 0; e < E; ++e) {
-        const float w = __shfl_xor(a[e], m);
-        a[e] = keep_min ? fminf(a[e], w) : fmaxf(a[e], w);
-      }
-    }
-#pragma unroll
-    for (int jj = E / 2; jj >= 1; jj >>= 1) {
-      if (uint32_t(jj) < k) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-          if ((e & jj) == 0) {
-            const int f = e | jj;
-            const bool asc = ((uint32_t(lane) * E + e) & k) == 0;
-            const float lo = fminf(a[e], a[f]);
-            const float hi = fmaxf(a[e], a[f]);
-            a[e] = asc ? lo : hi;
-            a[f] = asc ? hi : lo;
-          }
-        }
-      }
-    }
-  }
-}
-
-// Padded LDS layout of the old window in the incremental path: 4 spare floats after
-// every 2^PS. With PS = log2(E) a thread's blocked E-float chunk sits E + 4 floats from
-// its neighbour's, an odd multiple of 16 B for E >= 8: the 8 lanes of each group of a
-// ds_write_b128 cover all 32 banks (no conflict), and float4 runs stay 16-byte aligned.
-template <int PS>
-__device__ __forceinline__ uint32_t pad(uint32_t i) { return i + ((i >> PS) << 2); }
-__host__ __device__ constexpr uint32_t padded_size(uint32_t n, int ps) { return n + ((n >> ps) << 2) + 4; }
-__host__ __device__ constexpr int pad_shift(int E) { return E >= 32 ? 5 : E >= 16 ? 4 : E >= 8 ? 3 : 6; }
-
-// Layout of the merged window in the walk path: 1 spare float after every 16, so the
-// blocked scatter (lanes ~16 floats apart) hits 32 distinct banks with ds_write_b32.
-__device__ __forceinline__ uint32_t pad2(uint32_t i) { return i + (i >> 4); }
-__host__ __device__ constexpr uint32_t padded2_size(uint32_t n) { return n + (n >> 4) + 1; }
-
-template <int PS>
-__device__ inline uint32_t upper_bound_p(const float* a, uint32_t n, float x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a[pad<PS>(mid)] <= x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-// 64-ary upper_bound by a whole wave over an ascending (padded) LDS array: each round
-// every lane tests one pivot and a ballot narrows the range 64-fold; the result is uniform.
-template <int PS>
-__device__ inline uint32_t wave_upper_bound(const float* a, uint32_t n, float x, int lane) {
-  uint32_t lo = 0, len = n;
-  while (len > 64) {
-    uint32_t step = (len + 63) / 64;
-    step += (step & 7u) == 0 ? 1u : 0u;  // pivots a multiple of 8 apart would share 2 LDS banks
-    const uint32_t i = lo + uint32_t(lane) * step;
-    const bool before = i < lo + len && a[pad<PS>(i)] <= x;
-    const uint32_t c = __popcll(__ballot(before));  // chunks whose first element is <= x
-    if (c == 0) return lo;
-    const uint32_t end = lo + len;
-    lo += (c - 1) * step;
-    len = (lo + step < end ? lo + step : end) - lo;
-  }
-  const bool before = uint32_t(lane) < len && a[pad<PS>(lo + lane)] <= x;
-  return lo + __popcll(__ballot(before));
-}
-
-__device__ inline uint32_t lower_bound_u(const uint32_t* a, uint32_t n, uint32_t x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a[mid] < x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
-__device__ inline uint32_t upper_bound_u(const uint32_t* a, uint32_t n, uint32_t x) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a[mid] <= x) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // Value at position p of the merged window, found by binary searches (incremental path,
 // windows too long for a second LDS buffer): entering sample a if it lands on p, else
 // kept element m = p - a of the old window.
 template <int PS>
 __device__ inline float merged_at(const float* lds, const float* abuf, const uint32_t* pnew, const uint32_t* padj,
                                   uint32_t ka, uint32_t kr, uint32_t p) {
-  const uint32_t a = lower_bound_u(pnew, ka, p);
+  const uint32_t a = bound<false>(pnew, 0u, ka, p);
   if (a < ka && pnew[a] == p) return abuf[a];
   const uint32_t m = p - a;
-  return lds[pad<PS>(m + upper_bound_u(padj, kr, m))];
+  return lds[pad<PS>(m + bound<true>(padj, 0u, kr, m))];
 }
-
-// The series state through the vector memory path (a buffer load into VGPRs). A plain
-// load of this uniform address becomes a scalar load whose SGPRs the compiler spills
-// to VGPR lanes at once - waiting for the load right there, before the incremental
-// path's own loads could go out; in VGPRs it is first waited for where it is used.
-__device__ inline SeriesState load_state_vmem(const SeriesState* p) {
-  const __amdgpu_buffer_rsrc_t r =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<SeriesState*>(p), 0, int(sizeof(SeriesState)), 0x00020000);
-  const auto a = __builtin_amdgcn_raw_buffer_load_b128(r, 0, 0, 0);  // head (lo, hi), n, nvalid
-  const auto b = __builtin_amdgcn_raw_buffer_load_b64(r, 16, 0, 0);   // cur, valid
-  SeriesState s;
-  s.head = uint64_t(a[0]) | (uint64_t(a[1]) << 32);
-  s.n = a[2];
-  s.nvalid = a[3];
-  s.cur = b[0];
-  s.valid = b[1];
-  return s;
-}
-
-// One series as the kernel sees it: its ring's descriptor fields + its column.
-struct SeriesView {
-  float* base;
-  const float* host_rows;
-  float* sorted;
-  SeriesState* state;
-  const float* inl;  // &ring.inl[0][col]; row r at inl[r * kMaxInlineWidth]
-  uint64_t head, pred_head0;
-  uint32_t stride, col, mask, n, sorted_cap, host_mask, pred_n0, pred_cur, n_inline, ri, first, cols;
-};
-
-// The workgroup of column `col` of ring `ri` (blockIdx.x, blockIdx.y): its ring's
-// fields come from ONE round of scalar loads at an offset known at launch - no kernarg
-// load waits for another (a series -> ring search over the rings' column counts did:
-// two dependent kernel-argument round trips before the first global load).
-// RingDesc's fields before the inline rows, in the same order: copied in one go, so the
-// compiler issues every scalar load of the ring before the first use waits for any.
-struct RingHead {
-  float* base;
-  const float* host_rows;
-  float* sorted;
-  SeriesState* state;
-  uint64_t head, pred_head0;
-  uint32_t stride, cols, first, mask, n, sorted_cap, host_mask, pred_n0, pred_cur, n_inline;
-};
-static_assert(sizeof(RingHead) == offsetof(RingDesc, inl), "RingHead must mirror RingDesc's leading fields");
-
-__device__ inline SeriesView make_view(const StatsArgs& args, uint32_t ri, uint32_t col) {
-  RingHead R;
-  __builtin_memcpy(&R, &args.rings[ri], sizeof R);
-  SeriesView v;
-  v.base = R.base;
-  v.host_rows = R.host_rows;
-  v.sorted = R.sorted;
-  v.state = R.state;
-  v.head = R.head;
-  v.pred_head0 = R.pred_head0;
-  v.stride = R.stride;
-  v.mask = R.mask;
-  v.n = R.n;
-  v.sorted_cap = R.sorted_cap;
-  v.host_mask = R.host_mask;
-  v.pred_n0 = R.pred_n0;
-  v.pred_cur = R.pred_cur;
-  v.n_inline = R.n_inline;
-  v.col = col;
-  v.ri = ri;
-  v.first = R.first;
-  v.cols = R.cols;
-  v.inl = &args.rings[ri].inl[0][0];  // indexed, not selected: keeps the kernarg a kernarg
-  if (v.sorted) v.sorted += size_t(col) * 2 * v.sorted_cap;
-  if (v.state) v.state += col;
-  v.inl += col < uint32_t(kMaxInlineWidth) ? col : 0u;
-  if (col >= uint32_t(kMaxInlineWidth)) v.n_inline = 0;
-  return v;
-}
-
-// Sample `row` of a series: the newest rows by value from the kernel argument,
-// older entering rows from the pinned host ring in pull mode - both then also stored
-// into the device ring for the launch that later removes them - else from the device
-// ring the host filled with hipMemcpyAsync.
-__device__ inline float take_sample(const SeriesView& d, uint64_t row) {
-  float x;
-  if (row + d.n_inline >= d.head) {
-    x = d.inl[(row + d.n_inline - d.head) * kMaxInlineWidth];  // by value, in the kernarg
-  } else if (d.host_rows != nullptr) {
-    x = d.host_rows[(row & d.host_mask) * d.stride + d.col];
-  } else {
-    return d.base[(row & d.mask) * d.stride + d.col];
-  }
-  d.base[(row & d.mask) * d.stride + d.col] = x;
-  return x;
-}
-
-// The entering sample `row` without storing it (every thread of the one-row path reads
-// it; thread 0 stores it): `store` tells whether it still has to go into the device ring.
-__device__ inline float peek_sample(const SeriesView& d, uint64_t row, bool& store) {
-  store = true;
-  if (row + d.n_inline >= d.head) return d.inl[(row + d.n_inline - d.head) * kMaxInlineWidth];
-  if (d.host_rows != nullptr) return d.host_rows[(row & d.host_mask) * d.stride + d.col];
-  store = false;
-  return d.base[(row & d.mask) * d.stride + d.col];
-}
-
-// Bits that hold a count in [0, E].
-__host__ __device__ constexpr int count_bits(int e) { return e <= 1 ? 1 : 1 + count_bits(e >> 1); }
 
 // One wave: read k (<= 64*E) consecutive ring rows of a series starting at `first`,
 // sort them ascending (NaN and padding -> +inf, counted out) and store 64*E floats to
@@ -323,7 +116,7 @@ __device__ inline void load_sort_store(const SeriesView& d, uint64_t first, uint
     // readlanes, the values that precede its own; no 21-stage shuffle network
     float v = INFINITY;
     if (uint32_t(lane) < k) {
-      const float x = entering ? take_sample(d, first + lane) : d.base[((first + lane) & d.mask) * d.stride + d.col];
+      const float x = entering ? take_sample(d, first + lane) : ring_sample(d, first + lane);
       if (entering && uint32_t(lane) == k - 1) *lastv = x;
       if (!isnan(x)) {
         v = x;
@@ -351,7 +144,7 @@ __device__ inline void load_sort_store(const SeriesView& d, uint64_t first, uint
     float v = INFINITY;
     if (i < k) {
       // leaving rows are always in the device ring; entering rows come from the source
-      const float x = entering ? take_sample(d, first + i) : d.base[((first + i) & d.mask) * d.stride + d.col];
+      const float x = entering ? take_sample(d, first + i) : ring_sample(d, first + i);
       if (entering && i == k - 1) *lastv = x;  // newest raw sample (may be NaN)
       if (!isnan(x)) {
         v = x;
@@ -368,59 +161,6 @@ __device__ inline void load_sort_store(const SeriesView& d, uint64_t first, uint
   for (int off = 32; off >= 1; off >>= 1) {
     valid += __shfl_xor(valid, off);
     sum += __shfl_xor(sum, off);
-  }
-}
-
-// Wave64 sums through DPP (VALU lane moves, no LDS pipeline): xor 1 and xor 2 inside
-// each quad, the half-row and row mirrors, so every lane of a 16-lane row holds the row
-// sum; the four row sums are then read from lanes 0 / 16 / 32 / 48. (The shuffles they
-// replace were ds_bpermute round trips, 12 dependent ones for one double.)
-template <int Ctrl>
-__device__ __forceinline__ double dpp_f64(double v) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, int(uint32_t(u)), Ctrl, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, int(uint32_t(u >> 32)), Ctrl, 0xF, 0xF, false);
-  return __builtin_bit_cast(double, uint64_t(uint32_t(lo)) | (uint64_t(uint32_t(hi)) << 32));
-}
-
-__device__ inline double wave_sum(double v) {
-  v += dpp_f64<0xB1>(v);   // quad_perm [1, 0, 3, 2]
-  v += dpp_f64<0x4E>(v);   // quad_perm [2, 3, 0, 1]
-  v += dpp_f64<0x141>(v);  // row_half_mirror
-  v += dpp_f64<0x140>(v);  // row_mirror
-  const uint64_t u = __builtin_bit_cast(uint64_t, v);
-  double r = 0.0;
-#pragma unroll
-  for (int row = 0; row < 4; ++row) {
-    const uint32_t lo = uint32_t(__builtin_amdgcn_readlane(int(uint32_t(u)), 16 * row));
-    const uint32_t hi = uint32_t(__builtin_amdgcn_readlane(int(uint32_t(u >> 32)), 16 * row));
-    r += __builtin_bit_cast(double, uint64_t(lo) | (uint64_t(hi) << 32));
-  }
-  return r;
-}
-
-__device__ inline uint32_t wave_sum(uint32_t v) {
-  v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0xB1, 0xF, 0xF, false));
-  v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x4E, 0xF, 0xF, false));
-  v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x141, 0xF, 0xF, false));
-  v += uint32_t(__builtin_amdgcn_update_dpp(0, int(v), 0x140, 0xF, 0xF, false));
-  return uint32_t(__builtin_amdgcn_readlane(int(v), 0)) + uint32_t(__builtin_amdgcn_readlane(int(v), 16)) +
-         uint32_t(__builtin_amdgcn_readlane(int(v), 32)) + uint32_t(__builtin_amdgcn_readlane(int(v), 48));
-}
-
-// Sorted positions the outputs need: [min, max, lo0, hi0, lo1, hi1, lo2, hi2].
-__device__ inline void wanted_positions(uint32_t nv, const double qfrac[3], uint32_t (&idx)[8], float (&frac)[3]) {
-  const uint32_t last = nv ? nv - 1 : 0;
-  idx[0] = 0;
-  idx[1] = last;
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const double pos = qfrac[q] * double(last);  // qfrac = double(pct) / 100, host-computed
-    uint32_t lo = uint32_t(floor(pos));
-    if (lo > last) lo = last;
-    idx[2 + 2 * q] = lo;
-    idx[3 + 2 * q] = lo + 1 < nv ? lo + 1 : last;
-    frac[q] = float(pos - double(lo));
   }
 }
 
@@ -490,17 +230,10 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
   // own loads (old window, leaving / entering rows) waits for it - it is first used
   // by their validation
   if (predicted) st = load_state_vmem(d.state);
-  bool inc = false;
-  uint32_t kadd = 0, krem = 0;
-  if (have_state && h1 >= h0 && n0 <= h0 && cur <= 1) {
-    const uint64_t s0 = h0 - n0;
-    if (s1 >= s0 && h1 - h0 <= uint64_t(kMaxIncremental) && s1 - s0 <= uint64_t(kMaxIncremental) &&
-        s0 + uint64_t(d.mask) + 1 >= h1 && n0 <= d.sorted_cap && n1 <= d.sorted_cap) {
-      inc = true;
-      kadd = uint32_t(h1 - h0);
-      krem = uint32_t(s1 - s0);
-    }
-  }
+  const IncStep step = have_state ? incremental_step(h0, n0, cur, h1, n1, uint64_t(d.mask) + 1, d.sorted_cap)
+                                  : IncStep{false, 0u, 0u};
+  bool inc = step.ok;
+  const uint32_t kadd = step.kadd, krem = step.krem;
   const bool inc_selected = inc;  // a fall-back below clears `inc`, not this
 
   double sum = 0.0;
@@ -542,11 +275,11 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
     // the leaving row is in the device ring; the entering one by value in the kernel
     // argument (or the pinned host ring): uniform addresses, loaded by every thread
     bool ring_store = false;
-    const float rs = krem ? d.base[(s0 & d.mask) * d.stride + d.col] : __builtin_nanf("");
+    const float rs = krem ? ring_sample(d, s0) : __builtin_nanf("");
     float as = __builtin_nanf("");
     if (kadd) {
-      if (h0 + d.n_inline >= d.head) {  // by value in the kernel argument: a scalar load
-        as = args.rings[d.ri].inl[h0 + d.n_inline - d.head][d.col];
+      if (sample_source(d, h0) == Source::Inline) {  // by value in the kernel argument: a scalar load
+        as = args.rings[ring].inl[h0 + d.n_inline - d.head][d.col];
         ring_store = true;
       } else {
         as = peek_sample(d, h0, ring_store);
@@ -601,7 +334,7 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
     __syncthreads();
     WS_STAMP(2);
     if (t == 0 && kadd) {  // after the barrier: no load of the phase above waits for it
-      if (ring_store) d.base[(h0 & d.mask) * d.stride + d.col] = as;  // for the launch it leaves in
+      if (ring_store) ring_sample(d, h0) = as;  // for the launch it leaves in
       lastv = as;  // newest raw sample (may be NaN)
     }
     uint32_t lt = 0, le = 0, la = 0;
@@ -628,35 +361,26 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
       onerow = true;
       nv = n0v - kr + ka;
       wanted_positions(nv, args.qfrac, idx, frac);
-      const uint32_t x = kr ? le - 1u : 0xFFFFFFFFu;  // old position of the leaving sample
-      const uint32_t pn = ka ? la - (x < la ? 1u : 0u) : 0xFFFFFFFFu;  // new position of the entering one
-      uint32_t lo = x;
-      if (ka && la < lo) lo = la;
-      uint32_t hi = nv;
-      if (kr == ka) {
-        hi = kr ? x + 1u : 0u;
-        if (ka && la > hi) hi = la;
-        if (hi > nv) hi = nv;
-      }
+      const OneRowMap map = one_row_map(kr, ka, le - 1u, la);
+      const Span span = changed_span(kr, ka, map.x, map.x, la, la, nv);
       // new groups: position p takes the entering sample or the kept old element
-      // m + (x <= m), m = p - (pn < p): one of the old elements p - 1, p, p + 1
+      // map.src(p): one of the old elements p - 1, p, p + 1
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         const uint32_t q = 4u * (uint32_t(t) + uint32_t(NT) * g);
         float4 v4 = make_float4(xs[g][0], xs[g][1], xs[g][2], xs[g][3]);
         // only groups that meet [lo, hi) change (outside the span the values stay, past
         // nv the buffer is don't-care); whole waves outside it skip the shift
-        if (q < hi && q + 4u > lo) {
+        if (q < span.hi && q + 4u > span.lo) {
           float nw[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const uint32_t p = q + uint32_t(e);
-            const uint32_t m = p - (pn < p ? 1u : 0u);
-            const uint32_t src = m + (x <= m ? 1u : 0u);
+            const uint32_t src = map.src(p);
             const float prev = e == 0 ? left[g] : xs[g][e - 1];
             const float next = e == 3 ? right[g] : xs[g][e + 1];
             const float v = src < p ? prev : (src == p ? xs[g][e] : next);
-            nw[e] = p == pn ? as : v;
+            nw[e] = p == map.pn ? as : v;
           }
           v4 = make_float4(nw[0], nw[1], nw[2], nw[3]);
           *reinterpret_cast<float4*>(Sres + q) = v4;  // cap % 4 == 0: never past the half
@@ -748,7 +472,7 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
           const uint32_t j = item;
           const float r = rbuf[j];
           const uint32_t ub = wave_upper_bound<PS>(lds, n0v, r, lane);
-          const uint32_t c = upper_bound(rbuf, j, kr, r);  // equal leaving samples before + incl. j's run end
+          const uint32_t c = bound<true>(rbuf, j, kr, r);  // equal leaving samples before + incl. j's run end
           if (lane == 0) {
             const bool ok = ub + j >= c && ub + j - c < n0v && lds[pad<PS>(ub + j - c)] == r;
             if (!ok) bad = 1;  // state does not hold this sample
@@ -765,13 +489,13 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
         if (item < kr) {
           const uint32_t j = item;
           const float r = rbuf[j];
-          const uint32_t ub = upper_bound_p<PS>(lds, n0v, r);
-          const uint32_t c = upper_bound(rbuf, j, kr, r);
+          const uint32_t ub = bound<true>(lds, 0u, n0v, r, Padded<PS>{});
+          const uint32_t c = bound<true>(rbuf, j, kr, r);
           const bool ok = ub + j >= c && ub + j - c < n0v && lds[pad<PS>(ub + j - c)] == r;
           if (!ok) bad = 1;
           prem[j] = ok ? ub + j - c : 0u;
         } else {
-          qins[item - kr] = upper_bound_p<PS>(lds, n0v, abuf[item - kr]);
+          qins[item - kr] = bound<true>(lds, 0u, n0v, abuf[item - kr], Padded<PS>{});
         }
       }
     }
@@ -788,14 +512,10 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
       //     out nothing moved past the last one either. That span is rewritten in
       //     place in the resident buffer; consecutive lanes take consecutive positions
       //     (coalesced stores).
-      uint32_t lo = kr ? prem[0] : 0xFFFFFFFFu;
-      if (ka && qins[0] < lo) lo = qins[0];
-      uint32_t hi = nv;
-      if (kr == ka) {
-        hi = kr ? prem[kr - 1] + 1 : 0u;
-        if (ka && qins[ka - 1] > hi) hi = qins[ka - 1];
-        if (hi > nv) hi = nv;
-      }
+      const bool even = kr == ka;  // the last change points are read only then
+      const Span span = changed_span(kr, ka, kr ? prem[0] : 0u, even && kr ? prem[kr - 1] : 0u, ka ? qins[0] : 0u,
+                                     even && ka ? qins[ka - 1] : 0u, nv);
+      const uint32_t lo = span.lo, hi = span.hi;
       float* Sres = d.sorted + size_t(cur) * d.sorted_cap;
       // Entering sample j lands on pnew[j] = qins[j] - #(prem < qins[j]) + j; the m-th
       // kept old element sits at old index m + #(padj <= m), padj[r] = prem[r] - r.
@@ -803,14 +523,9 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
         // (3a) at most one sample out and one in (the steady state: one new row per
         //      refresh): the span is a shift by one around the entering sample, each
         //      position gathered from its source - no merge buffer, no barrier
-        const uint32_t x = kr ? prem[0] : 0xFFFFFFFFu;  // old position of the leaving sample
-        const uint32_t pn = ka ? qins[0] - (x < qins[0] ? 1u : 0u) : 0xFFFFFFFFu;  // new position of the entering one
+        const OneRowMap map = one_row_map(kr, ka, kr ? prem[0] : 0u, ka ? qins[0] : 0u);
         const float av = ka ? abuf[0] : 0.f;
-        auto at = [&](uint32_t p) -> float {
-          if (p == pn) return av;
-          const uint32_t m = p - (pn < p ? 1u : 0u);  // kept-element index
-          return lds[pad<PS>(m + (x <= m ? 1u : 0u))];
-        };
+        auto at = [&](uint32_t p) -> float { return p == map.pn ? av : lds[pad<PS>(map.src(p))]; };
         for (uint32_t p = lo + uint32_t(t); p < hi; p += NT) Sres[p] = at(p);
         if (t < 8) wv[t] = at(idx[t]);
       } else if constexpr (kLdsOut) {
@@ -818,8 +533,8 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
         //      rank = i - #leaving before i + #entering before i, both counts changing
         //      only at the <= 2k change points - and scatters it into the merge buffer
         //      (conflict-free padding); then the span is copied out
-        uint32_t r = lower_bound_u(prem, kr, b);  // leaving positions < b
-        uint32_t q = upper_bound_u(qins, ka, b);  // insertion points <= b
+        uint32_t r = bound<false>(prem, 0u, kr, b);  // leaving positions < b
+        uint32_t q = bound<true>(qins, 0u, ka, b);  // insertion points <= b
         uint32_t next_r = r < kr ? prem[r] : 0xFFFFFFFFu;
         uint32_t next_q = q < ka ? qins[q] : 0xFFFFFFFFu;
 #pragma unroll
@@ -840,7 +555,7 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
         }
         for (uint32_t j = t; j < ka; j += NT) {
           const uint32_t qj = qins[j];
-          lds2[pad2(qj - lower_bound_u(prem, kr, qj) + j)] = abuf[j];
+          lds2[pad2(qj - bound<false>(prem, 0u, kr, qj) + j)] = abuf[j];
         }
         __syncthreads();
         // span copy-out in aligned float4s (positions of [lo & ~3, hi) outside the span
@@ -858,7 +573,7 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
         if (t < 8) wv[t] = lds2[pad2(idx[t])];
       } else {
         // (3c) more samples, window too long for a merge buffer: binary searches
-        for (uint32_t j = t; j < ka; j += NT) pnew[j] = qins[j] - lower_bound_u(prem, kr, qins[j]) + j;
+        for (uint32_t j = t; j < ka; j += NT) pnew[j] = qins[j] - bound<false>(prem, 0u, kr, qins[j]) + j;
         for (uint32_t j = t; j < kr; j += NT) padj[j] = prem[j] - j;
         __syncthreads();
         for (uint32_t p = lo + uint32_t(t); p < hi; p += NT) Sres[p] = merged_at<PS>(lds, abuf, pnew, padj, ka, kr, p);
@@ -910,42 +625,18 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
         }
       }
       // (2) partner in the same wave: lane xor m, m in [1, 32].
-      for (; j >= uint32_t(E); j >>= 1) {
-        const int m = int(j / E);
-        const bool keep_min = ((t & m) == 0) == (((uint32_t(t) * E) & k) == 0);
-#pragma unroll
-        for (int e = 0; e < E; ++e) {
-          const float w = __shfl_xor(a[e], m);
-          a[e] = keep_min ? fminf(a[e], w) : fmaxf(a[e], w);
-        }
-      }
+      for (; j >= uint32_t(E); j >>= 1) cx_in_wave<E>(a, k, j, uint32_t(t) * E);
       // (3) partner in the same thread: compile-time register pairs.
-#pragma unroll
-      for (int jj = E / 2; jj >= 1; jj >>= 1) {
-        if (uint32_t(jj) < k) {
-#pragma unroll
-          for (int e = 0; e < E; ++e) {
-            if ((e & jj) == 0) {
-              const int f = e | jj;
-              const bool asc = ((uint32_t(t) * E + e) & k) == 0;
-              const float lo = fminf(a[e], a[f]);
-              const float hi = fmaxf(a[e], a[f]);
-              a[e] = asc ? lo : hi;
-              a[f] = asc ? hi : lo;
-            }
-          }
-        }
-      }
+      cx_in_thread<E>(a, k, uint32_t(t) * E);
     }
     __syncthreads();  // last LDS-stage reads are done before the buffer is rewritten
 #pragma unroll
     for (int e = 0; e < E; ++e) lds[t * E + e] = a[e];
   }
 
-  // the incremental path updates half `cur` in place; a full sort (first refresh or
-  // rebuild) writes the other half (or half 0 without state). A fall-back from the
-  // incremental path keeps `cur`: its sort does not read the resident window.
-  auto next_half = [&]() -> uint32_t { return inc_selected ? cur : (st.valid ? (st.cur ^ 1u) : 0u); };
+  // the half this launch leaves current (a fall-back from the incremental path keeps the
+  // half it was selected for)
+  auto half = [&]() -> uint32_t { return next_half(inc_selected, st.valid != 0, inc_selected ? cur : st.cur); };
 
   // ---- reductions (both paths): sum and count per wave, then across waves --------
   const double ds = wave_sum(sum);
@@ -968,7 +659,7 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
     wanted_positions(nv, args.qfrac, idx, frac);
     if (t < 8) wv[t] = lds[idx[t]];
     if (d.sorted != nullptr) {  // seed the resident state with the sorted window
-      float* Sout = d.sorted + size_t(next_half()) * d.sorted_cap;
+      float* Sout = d.sorted + size_t(half()) * d.sorted_cap;
       for (uint32_t i = t; i < nv; i += NT) Sout[i] = lds[i];
     }
     __syncthreads();
@@ -978,7 +669,7 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
     ns.head = h1;
     ns.n = n1;
     ns.nvalid = nv;
-    ns.cur = next_half();
+    ns.cur = half();
     ns.valid = 1;
     *d.state = ns;
   }
@@ -993,7 +684,7 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
       r = float(nv);
     } else if (t == STAT_LAST) {
       // newest raw sample: captured by this launch unless no row entered the window
-      if (h1) r = (inc && kadd == 0) ? d.base[((h1 - 1) & d.mask) * d.stride + d.col] : lastv;
+      if (h1) r = (inc && kadd == 0) ? ring_sample(d, h1 - 1) : lastv;
     } else if (nv) {
       if (t == STAT_MIN) {
         r = order_stat(0);
@@ -1003,9 +694,7 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
         r = float(total / double(nv));
       } else {
         const int q = t - STAT_P0;
-        const double x0 = order_stat(2 + 2 * q), x1 = order_stat(3 + 2 * q);
-        const double f = frac[q];
-        r = float(f >= 0.5 ? x1 - (x1 - x0) * (1.0 - f) : x0 + (x1 - x0) * f);
+        r = percentile_between(order_stat(2 + 2 * q), order_stat(3 + 2 * q), frac[q]);
       }
     }
     // system-scope stores: written through to memory whatever the mapping of the
@@ -1037,21 +726,51 @@ __global__ __launch_bounds__(NT) void window_stats_kernel(const StatsArgs args, 
 template <int NT, int E>
 hipError_t launch(const StatsArgs& args, float* out, hipStream_t stream) {
   uint32_t max_cols = 0;
-  for (uint32_t r = 0; r < args.num_rings; ++r) max_cols = args.rings[r].cols > max_cols ? args.rings[r].cols : max_cols;
+  for (uint32_t r = 0; r < args.num_rings; ++r) max_cols = args.rings[r].h.cols > max_cols ? args.rings[r].h.cols : max_cols;
   hipLaunchKernelGGL((window_stats_kernel<NT, E>), dim3(max_cols, args.num_rings), dim3(NT), 0, stream, args, out);
   return hipGetLastError();
 }
 
-}  // namespace
 
-uint32_t sort_width_for(uint32_t n) {
-  uint32_t p = 64;
-  while (p < n) p <<= 1;
-  return p;
+// Every instantiation there is: the (threads, samples per thread) launch_shape can return.
+struct Launcher {
+  int nt, e;
+  hipError_t (*fn)(const StatsArgs&, float*, hipStream_t);
+};
+template <int NT, int E>
+constexpr Launcher launcher() { return {NT, E, &launch<NT, E>}; }
+constexpr Launcher kLaunchers[] = {
+    launcher<64, 1>(),   launcher<128, 1>(),  launcher<256, 1>(),  launcher<512, 1>(),   launcher<1024, 1>(),
+    launcher<1024, 2>(), launcher<256, 2>(),  launcher<256, 4>(),  launcher<512, 4>(),   launcher<512, 8>(),
+    launcher<1024, 4>(), launcher<512, 16>(), launcher<1024, 8>(), launcher<1024, 16>(), launcher<1024, 32>(),
+};
+constexpr bool has_launcher(LaunchShape s) {
+  for (const Launcher& l : kLaunchers)
+    if (l.nt == s.nt && l.e == s.e) return true;
+  return false;
+}
+constexpr bool every_shape_has_a_launcher() {
+  for (uint32_t w = 64; w <= 32768; w <<= 1)
+    for (uint32_t rows : {0u, ~0u})
+      if (!has_launcher(launch_shape(w, false, rows, 0)) || !has_launcher(launch_shape(w, true, rows, 0))) return false;
+  return true;
+}
+static_assert(every_shape_has_a_launcher(), "launch_shape returns a shape kLaunchers does not hold");
+
+int launch_sized(const StatsArgs& args, uint32_t pad_pow2, float* out, hipStream_t stream, bool incremental,
+                 uint32_t max_new_rows) {
+  // ROCMDASH_SMALL_K_ROWS moves launch_shape's few-rows threshold for A/B runs
+  static const uint32_t small_k = [] {
+    const char* e = std::getenv("ROCMDASH_SMALL_K_ROWS");
+    return e ? uint32_t(std::strtoul(e, nullptr, 10)) : 2u;
+  }();
+  const LaunchShape s = launch_shape(pad_pow2, incremental, max_new_rows, small_k);
+  for (const Launcher& l : kLaunchers)
+    if (l.nt == s.nt && l.e == s.e) return l.fn(args, out, stream);
+  return hipErrorInvalidValue;
 }
 
-static int launch_sized(const StatsArgs& args, uint32_t pad_pow2, float* out, hipStream_t stream, bool incremental,
-                        uint32_t max_new_rows);
+}  // namespace
 
 int launch_window_stats(const StatsArgs& args, uint32_t pad_pow2, float* out, void* stream_ptr, bool incremental,
                         uint32_t max_new_rows) {
@@ -1059,7 +778,7 @@ int launch_window_stats(const StatsArgs& args, uint32_t pad_pow2, float* out, vo
   if (args.num_series > uint32_t(kMaxSeriesPerLaunch)) return hipErrorInvalidValue;
   if (args.num_rings == 0 || args.num_rings > uint32_t(kMaxRingsPerLaunch)) return hipErrorInvalidValue;
   for (uint32_t i = 0; i < args.num_rings; ++i) {  // host-side shape checks before any launch
-    const RingDesc& r = args.rings[i];
+    const RingHead& r = args.rings[i].h;
     if (r.n > pad_pow2 || r.n > r.mask + 1 || r.n > r.head || ((r.mask + 1) & r.mask) || r.stride == 0) return hipErrorInvalidValue;
     if (r.sorted != nullptr && (r.state == nullptr || r.sorted_cap < r.n || r.sorted_cap > pad_pow2)) return hipErrorInvalidValue;
     if (r.n_inline > uint32_t(kInlineRows) || r.n_inline > r.head) return hipErrorInvalidValue;
@@ -1068,56 +787,15 @@ int launch_window_stats(const StatsArgs& args, uint32_t pad_pow2, float* out, vo
   }
   uint32_t cols = 0;
   for (uint32_t i = 0; i < args.num_rings; ++i) {
-    if (args.rings[i].cols > args.rings[i].stride) return hipErrorInvalidValue;
-    cols += args.rings[i].cols;
+    if (args.rings[i].h.cols > args.rings[i].h.stride) return hipErrorInvalidValue;
+    cols += args.rings[i].h.cols;
   }
   if (cols != args.num_series) return hipErrorInvalidValue;  // series = the rings' columns, in ring order
   auto stream = static_cast<hipStream_t>(stream_ptr);
   StatsArgs a = args;
   for (int q = 0; q < 3; ++q) a.qfrac[q] = double(a.pct[q]) / 100.0;
-  for (uint32_t i = 0, first = 0; i < a.num_rings; first += a.rings[i].cols, ++i) a.rings[i].first = first;
+  for (uint32_t i = 0, first = 0; i < a.num_rings; first += a.rings[i].h.cols, ++i) a.rings[i].h.first = first;
   return launch_sized(a, pad_pow2, out, stream, incremental, max_new_rows);
-}
-
-static int launch_sized(const StatsArgs& args, uint32_t pad_pow2, float* out, hipStream_t stream, bool incremental,
-                        uint32_t max_new_rows) {
-  if (incremental && pad_pow2 > 256 && pad_pow2 <= 8192) {
-    // Steady state: every series is expected to take the incremental path. With at
-    // most one row in (the one-row path) 512 threads - two waves per SIMD overlap
-    // each other's dependent instructions - measured fastest; the general merge of
-    // k > 1 rows gains from 1024 (HIP events, W = 4096 x 15: k = 1 8.5 vs 9.1 us at
-    // 512 vs 1024 threads, k = 10 15.4 vs 14.0 us; profiles/r02/onerow/). (A series
-    // whose state turns out invalid still sorts correctly, with E = P / NT.)
-    // (free-running sampling brings 2 rows of the faster source into many refreshes:
-    // the series with one row keep the one-row path, those with two take the general
-    // path at 512 threads - ROCMDASH_SMALL_K_ROWS moves the threshold for A/B runs)
-    static const uint32_t small_k = [] {
-      const char* e = std::getenv("ROCMDASH_SMALL_K_ROWS");
-      return e ? uint32_t(std::strtoul(e, nullptr, 10)) : 2u;
-    }();
-    const bool one_row = max_new_rows <= small_k;
-    switch (pad_pow2) {
-      case 512: return launch<256, 2>(args, out, stream);
-      case 1024: return launch<256, 4>(args, out, stream);
-      case 2048: return launch<512, 4>(args, out, stream);
-      case 4096: return one_row ? launch<512, 8>(args, out, stream) : launch<1024, 4>(args, out, stream);
-      case 8192: return one_row ? launch<512, 16>(args, out, stream) : launch<1024, 8>(args, out, stream);
-      default: break;
-    }
-  }
-  switch (pad_pow2) {
-    case 64: return launch<64, 1>(args, out, stream);
-    case 128: return launch<128, 1>(args, out, stream);
-    case 256: return launch<256, 1>(args, out, stream);
-    case 512: return launch<512, 1>(args, out, stream);
-    case 1024: return launch<1024, 1>(args, out, stream);
-    case 2048: return launch<1024, 2>(args, out, stream);
-    case 4096: return launch<1024, 4>(args, out, stream);
-    case 8192: return launch<1024, 8>(args, out, stream);
-    case 16384: return launch<1024, 16>(args, out, stream);
-    case 32768: return launch<1024, 32>(args, out, stream);
-    default: return hipErrorInvalidValue;
-  }
 }
 
 }  // namespace rocmdash

@@ -157,6 +157,58 @@ def test_incremental_window_path_matches_reference(native, cuda, W, dist, pull):
     np.testing.assert_allclose(out.cpu().numpy(), window_stats_reference(rows.T), rtol=1e-5, atol=1e-4)
 
 
+@pytest.mark.parametrize("W,dist", [(2048, "ties"), (8192, "ties"), (8192, "normal"), (16384, "ties"), (16384, "normal"),
+                                    (32768, "ties"), (32768, "normal")])
+def test_incremental_window_path_wide_windows(native, cuda, W, dist):
+    """The incremental path at the widths whose kernel instantiations the test above
+    never runs incrementally (the instantiation is a function of W alone): <512,4>,
+    <512,16> / <1024,8>, <1024,16> and <1024,32> - the register walk at E >= 8 and, at
+    W = 32768, the merge by binary searches. Every refresh must equal the fp64
+    reference, and the resident window must end as exactly the sorted window."""
+    import torch
+
+    from rocmdash.ops.window_stats import window_stats_reference
+
+    nat = native
+    nat.set_pinned_host_rings(True)
+    nat.set_pull_mode(True)
+    ring = nat.SeriesRing(6, 8 * W)
+    dws = nat.DeviceWindowSet(W, 0)
+    dws.add_ring(ring)
+    out = torch.empty((6, 8), device=cuda)
+    exp = torch.empty((6, 1 + W), device=cuda)
+    rng = np.random.default_rng(W)
+    stream = torch.cuda.current_stream().cuda_stream
+    t = 0
+    adds = [W + 3, 1, 1, 0, 2, 17, 255, 256, 257, 1, 64, 5, 1, 0, 128]
+    for it, add in enumerate(adds):
+        if add:
+            if dist == "ties":
+                x = rng.integers(0, 6, (add, 6)).astype(np.float32)
+            else:
+                x = rng.normal(100, 20, (add, 6)).astype(np.float32)
+            x[rng.random((add, 6)) < 0.05] = np.nan
+            x[:, 5] = -x[:, 5]
+            ring.push_many(x, np.arange(t + 1, t + 1 + add, dtype=np.uint64))
+            t += add
+        dws.refresh(out.data_ptr(), stream)
+        torch.cuda.synchronize()
+        rows, _ = ring.window(W)
+        ref = window_stats_reference(rows.T)
+        np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=1e-5, atol=1e-4, err_msg=f"iteration {it} add {add}")
+    st = dws.stats()
+    assert st["incremental_launches"] >= len(adds) // 2, st  # steady state is incremental
+    dws.export_sorted(exp.data_ptr(), stream)
+    torch.cuda.synchronize()
+    rows, _ = ring.window(W)
+    got = exp.cpu().numpy()
+    for s in range(6):
+        col = rows[:, s]
+        want = np.sort(col[~np.isnan(col)])
+        assert int(got[s, 0]) == len(want), s
+        np.testing.assert_array_equal(got[s, 1:1 + len(want)], want, err_msg=f"series {s}")
+
+
 def test_amdsmi_source_reads_plausible_values(native):
     nat = native
     assert nat.amdsmi_gpu_count() >= 1, "amd-smi sees no GPU on the box"
