@@ -126,6 +126,8 @@ PYBIND11_MODULE(_native, m) {
         d["clock_mhz"] = clk;
         return d;
       }, "Per-XCD busy (%) and gfx clock (MHz) of the last sample, or None")
+      .def("set_back_to_back", &Source::set_back_to_back, py::arg("on"),
+           "Hint that sample() is being polled back to back (what Sampler.start_free sets).")
       .def("sample", [](Source& s) -> py::object {
         py::array_t<float> row{py::ssize_t(s.width())};
         bool ok;
@@ -197,6 +199,23 @@ PYBIND11_MODULE(_native, m) {
       .def_property_readonly("attempts", &RawCalibrationPolicy::attempts)
       .def_property_readonly("promotions", &RawCalibrationPolicy::promotions)
       .def_property_readonly("last_matched", &RawCalibrationPolicy::last_matched);
+  py::class_<SmuTableTracker>(m, "SmuTableTracker",
+                              "When the SMI source reads the SMU table while polled back to back (CPU-testable).")
+      .def(py::init<int64_t, int64_t>(), py::arg("guard_ns") = kSmuGuardNs, py::arg("hard_ns") = kSmuHardNs)
+      .def("set_back_to_back", &SmuTableTracker::set_back_to_back, py::arg("on"))
+      .def("restart", &SmuTableTracker::restart)
+      .def("should_read", &SmuTableTracker::should_read, py::arg("now_ns"))
+      .def("record", &SmuTableTracker::record, py::arg("now_ns"), py::arg("changed"), py::arg("fw_ts") = 0)
+      .def_property_readonly("state", [](const SmuTableTracker& t) { return int(t.state()); })
+      .def_property_readonly("period_ns", &SmuTableTracker::period_ns)
+      .def_property_readonly("guard_ns", &SmuTableTracker::guard_ns)
+      .def_property_readonly("hard_ns", &SmuTableTracker::hard_ns)
+      .def_property_readonly("changes", &SmuTableTracker::changes)
+      .def_property_readonly("locks", &SmuTableTracker::locks)
+      .def_property_readonly("resyncs", &SmuTableTracker::resyncs)
+      .def_property_readonly("missed", &SmuTableTracker::missed);
+  m.attr("SMU_GUARD_NS") = kSmuGuardNs;
+  m.attr("SMU_HARD_NS") = kSmuHardNs;
   m.def("counters_ready", &counters_ready);
   m.def("counters_status", &counters_status);
 
@@ -525,6 +544,7 @@ PYBIND11_MODULE(_native, m) {
     return py::make_tuple(std::vector<uint32_t>(idx, idx + 8), std::vector<float>(frac, frac + 3));
   });
   m.def("ws_percentile_between", &percentile_between, py::arg("x0"), py::arg("x1"), py::arg("frac"));
+  m.attr("WS_INLINE_ROWS") = kInlineRows;  // most entering rows per ring sent in the kernel argument
   m.def("ws_launch_shape", [](uint32_t pad_pow2, bool incremental, uint32_t max_new_rows, uint32_t small_k) {
     const LaunchShape s = launch_shape(pad_pow2, incremental, max_new_rows, small_k);
     return py::make_tuple(s.nt, s.e);

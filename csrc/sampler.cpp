@@ -204,6 +204,7 @@ void Sampler::start_free(double max_hz) {
     throw std::runtime_error("start_free() while a request() is pending or unwaited (SPSC ring)");
   free_min_ns_ = int64_t(1e9 / max_hz);
   free_.store(true);
+  src_->set_back_to_back(true);  // from here the source is polled back to back
   start();
 }
 
@@ -222,7 +223,7 @@ void Sampler::stop() {
   bool expected = true;
   if (!running_.compare_exchange_strong(expected, false)) return;
   if (th_.joinable()) th_.join();
-  free_.store(false);
+  if (free_.exchange(false)) src_->set_back_to_back(false);  // paced, closed-loop and direct reads: no hint
 }
 
 SamplerStats Sampler::counts() const {

@@ -406,11 +406,18 @@ class SmiSource final : public Source {
     else record_calibration(0, true, "disabled by ROCMDASH_SMI_RAW=0");
     info_.metrics_path = raw_ ? "sysfs" : "amdsmi";
     // The firmware publishes a new metrics table every ~20 ms (~50 / s); a table read
-    // (an SMU round trip, ~50 us) more often than this returns the previous table. With
-    // ROCMDASH_SMU_TABLE_MIN_US > 0 the table is read at most that often and rows in
-    // between repeat its values (as back-to-back reads do anyway); used VRAM - the live
-    // column - is still read on every sample.
+    // (an SMU round trip, ~50 us) more often than this returns the previous table. While
+    // a free-running sampler polls the source back to back (set_back_to_back) the raw
+    // path therefore reads the table only around the moment the next publication is due
+    // (SmuTableTracker, sources.h); rows in between repeat the last table (as back-to-back
+    // reads do anyway) and cost the used-VRAM read - the live column - alone.
+    // ROCMDASH_SMU_TABLE_TRACK=0 turns the tracking off. The amd-smi decoding path
+    // (sample_smi) stays untracked: it reads on every sample.
+    // With ROCMDASH_SMU_TABLE_MIN_US > 0 the table is instead read at most that often,
+    // in every sampling mode (a fixed hold: a publication is seen up to that much late);
+    // it wins over the tracking.
     if (const char* v = std::getenv("ROCMDASH_SMU_TABLE_MIN_US")) table_min_ns_ = int64_t(std::atof(v) * 1000.0);
+    track_enabled_ = !env_disabled("ROCMDASH_SMU_TABLE_TRACK");
   }
   ~SmiSource() override {
     if (vram_fd_ >= 0) ::close(vram_fd_);
@@ -433,23 +440,33 @@ class SmiSource final : public Source {
       info_.metrics_path = raw_ ? "sysfs" : "amdsmi";
     }
     bool any = false;
-    const int64_t now = table_min_ns_ > 0 ? std::chrono::duration_cast<std::chrono::nanoseconds>(
-                                                std::chrono::steady_clock::now().time_since_epoch()).count()
-                                          : 0;
-    if (table_min_ns_ > 0 && have_last_ && now - last_table_ns_ < table_min_ns_) {
+    // publication tracking: only back to back, on the raw path, without the fixed hold
+    const bool track = track_enabled_ && table_min_ns_ <= 0 && raw_ && back_to_back_.load(std::memory_order_relaxed);
+    tracker_.set_back_to_back(track);
+    const int64_t now = (table_min_ns_ > 0 || track) ? now_ns() : 0;
+    const bool hold = table_min_ns_ > 0 ? now - last_table_ns_ < table_min_ns_ : track && !tracker_.should_read(now);
+    if (have_last_ && hold) {
       std::memcpy(row, last_row_, sizeof last_row_);  // the table as last read
       ++table_skips_;
       any = true;
     } else {
       for (int i = 0; i < SMI_NUM_FIELDS; ++i) row[i] = kNaN;
-      any = raw_ && sample_raw(row);
+      bool changed = false;
+      uint64_t fw_ts = 0;
+      any = raw_ && sample_raw(row, &changed, &fw_ts);
+      if (track) {
+        if (any) tracker_.record(now, changed, fw_ts);
+        else tracker_.restart();  // the raw read failed: amd-smi decoded this row
+      }
       if (!any) any = sample_smi(row);
-      if (any && table_min_ns_ > 0) {
+      have_last_ = any && (table_min_ns_ > 0 || track);
+      if (have_last_) {
         std::memcpy(last_row_, row, sizeof last_row_);
         last_table_ns_ = now;
-        have_last_ = true;
       }
     }
+    if (track || was_tracking_) export_tracker();
+    was_tracking_ = track;
     uint64_t used_bytes = 0;
     if (vram_fd_ >= 0 && info_.vram_total_mb > 0 && read_u64_attr(vram_fd_, &used_bytes)) {
       any = true;
@@ -466,12 +483,27 @@ class SmiSource final : public Source {
     return any;
   }
   bool fast_vram() const { return vram_fd_ >= 0; }
+  void set_back_to_back(bool on) override {
+    back_to_back_.store(on, std::memory_order_relaxed);
+    // reported off at once; the tracker itself is reset by the next sample()
+    if (!on) track_state_.store(0, std::memory_order_relaxed);
+  }
   std::vector<std::pair<std::string, double>> counts() const override {
     return {{"raw_reads", double(raw_reads_.load(std::memory_order_relaxed))},
             {"raw_table_changes", double(raw_changes_.load(std::memory_order_relaxed))},
             {"raw_misses", double(raw_misses_.load(std::memory_order_relaxed))},
             {"table_skips", double(table_skips_.load(std::memory_order_relaxed))},
             {"table_min_us", double(table_min_ns_) / 1000.0},
+            // publication tracking (SmuTableTracker): 0 = off (not polled back to back, or
+            // disabled), 1 = acquiring the period, 2 = locked; the locked period; times the
+            // lock was lost; publications judged missed (an interval above 1.5 periods)
+            {"table_track", double(track_state_.load(std::memory_order_relaxed))},
+            {"table_track_enabled", track_enabled_ ? 1.0 : 0.0},
+            {"table_period_us", double(track_period_ns_.load(std::memory_order_relaxed)) / 1000.0},
+            {"table_locks", double(track_locks_.load(std::memory_order_relaxed))},
+            {"table_resyncs", double(track_resyncs_.load(std::memory_order_relaxed))},
+            {"table_missed", double(track_missed_.load(std::memory_order_relaxed))},
+            {"table_guard_us", double(kSmuGuardNs) / 1000.0},
             {"raw_volatile_words", double(volatile_words_.size())},
             {"raw_interconnect", raw_ic_ ? 1.0 : 0.0},
             {"raw_xcd", raw_xcd_ ? 1.0 : 0.0},
@@ -493,7 +525,9 @@ class SmiSource final : public Source {
  private:
   // blob -> row through the calibrated layout; false (=> amd-smi) if the table read
   // fails or its header is no longer the calibrated one
-  bool sample_raw(float* row) {
+  // `changed`: the firmware published a table since the previous read; `fw_ts`: the
+  // table's firmware timestamp (0 when the interconnect words are not read raw)
+  bool sample_raw(float* row, bool* changed, uint64_t* fw_ts) {
     const ssize_t n = ::pread(metrics_fd_, buf_.data(), buf_.size(), 0);
     if (n < raw_size_ || rd16(buf_.data(), 0) != raw_size_ || buf_[2] != raw_fmt_ || buf_[3] != raw_content_) {
       ++raw_misses_;
@@ -516,7 +550,9 @@ class SmiSource final : public Source {
         rdk[i] = rd64(b, I.xgmi_rd + 8 * i);
         wrk[i] = rd64(b, I.xgmi_wr + 8 * i);
       }
-      interconnect(rd64(b, I.fw_ts), rdk, wrk, rd64(b, I.pcie_inst), row);
+      const uint64_t ts = rd64(b, I.fw_ts);
+      interconnect(ts, rdk, wrk, rd64(b, I.pcie_inst), row);
+      if (ts != ~0ull) *fw_ts = ts;
     }
     if (raw_xcd_) {
       uint32_t busy[kMaxXcds];
@@ -533,6 +569,7 @@ class SmiSource final : public Source {
     for (uint32_t w : volatile_words_) std::memset(buf_.data() + 8 * size_t(w), 0, 8);
     if (std::memcmp(buf_.data(), prev_.data(), raw_size_) != 0) {
       ++raw_changes_;
+      *changed = true;
       std::memcpy(prev_.data(), buf_.data(), raw_size_);
     }
     return true;
@@ -555,6 +592,14 @@ class SmiSource final : public Source {
       return true;
     }
     return false;
+  }
+
+  void export_tracker() {
+    track_state_.store(int(tracker_.state()), std::memory_order_relaxed);
+    track_period_ns_.store(tracker_.period_ns(), std::memory_order_relaxed);
+    track_locks_.store(tracker_.locks(), std::memory_order_relaxed);
+    track_resyncs_.store(tracker_.resyncs(), std::memory_order_relaxed);
+    track_missed_.store(tracker_.missed(), std::memory_order_relaxed);
   }
 
   void interconnect(uint64_t fw_ts, const uint64_t* rd_kb, const uint64_t* wr_kb, uint64_t pcie_inst, float* row) {
@@ -709,6 +754,13 @@ class SmiSource final : public Source {
   uint8_t raw_fmt_ = 0, raw_content_ = 0;
   std::atomic<uint64_t> raw_misses_{0}, raw_reads_{0}, raw_changes_{0}, table_skips_{0};
   int64_t table_min_ns_ = 0;  // ROCMDASH_SMU_TABLE_MIN_US
+  bool track_enabled_ = true;  // ROCMDASH_SMU_TABLE_TRACK
+  std::atomic<bool> back_to_back_{false};  // the sampler's hint (any thread)
+  SmuTableTracker tracker_{kSmuGuardNs, kSmuHardNs};  // sampling thread only; exported below
+  bool was_tracking_ = false;
+  std::atomic<int> track_state_{0};
+  std::atomic<int64_t> track_period_ns_{0};
+  std::atomic<uint64_t> track_locks_{0}, track_resyncs_{0}, track_missed_{0};
   int64_t last_table_ns_ = 0;
   bool have_last_ = false;
   float last_row_[SMI_NUM_FIELDS];

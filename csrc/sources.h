@@ -87,6 +87,11 @@ class Source {
   // one per accelerator complex die (8 on an MI355X in SPX mode); NaN where the
   // firmware reports none. Empty for sources without it. Safe to call while sampling.
   virtual std::vector<float> xcd_detail() const { return {}; }
+  // Hint: sample() is (not) being called back to back by a free-running sampler thread
+  // (Sampler::start_free / stop). A source may then skip work whose result cannot have
+  // changed since the previous call (SmiSource's SMU table tracking); a direct sample()
+  // call, paced and closed-loop sampling never set it. Callable from any thread.
+  virtual void set_back_to_back(bool) {}
 };
 
 constexpr int kMaxXcds = 8;
@@ -151,6 +156,124 @@ class RawCalibrationPolicy {
   int attempts_ = 0, promotions_ = 0, last_matched_ = -1;
   int64_t last_ns_ = 0;
 };
+
+// When the SMU metrics table is worth reading (SmiSource, free-running sampling): the
+// firmware publishes a new table every ~20 ms while a back-to-back sampler asks ~20000
+// times a second, and every table read is an SMU mailbox round trip (~46 us) that
+// returns the previous table. The tracker learns the publication period from the reads'
+// outcomes and lets the source skip the reads that cannot return anything new:
+//   acquire  read on every sample until kLockIntervals consecutive publication intervals
+//            agree (within the guard), then lock with period P;
+//   locked   after a change seen at t_c skip until t_c + P - guard, then read on every
+//            sample until the change is seen (P follows the intervals, 1/8 at a time); no
+//            change by t_c + P + guard, or an interval that disagrees with P -> acquire.
+// Never more than `hard_ns` pass without a read. An interval is the host time between
+// the starts of the reads that saw the two changes. A change found by the FIRST read
+// after a skip cannot be placed in time (the table may have been published anywhere in
+// the skip, e.g. the cadence doubled), so it goes back to acquire as well. The table's
+// firmware timestamp (fw_ts, 10 ns units, when the caller has it) only judges whether a
+// publication was missed (an interval above 1.5 P): it does not stretch when the sampling
+// thread is held up, but it moves in ~1 ms steps on MI355X (2 % of its deltas are 19 or
+// 21 ms between publications the host sees 20.0 ms apart), too coarse to time the reads.
+// Tracking runs only while set_back_to_back(true): otherwise every sample reads.
+// Header-only and clock-free (the caller passes the time), unit-tested on the CPU.
+class SmuTableTracker {
+ public:
+  enum State : int { kOff = 0, kAcquire = 1, kLocked = 2 };
+  static constexpr int kLockIntervals = 3;
+  explicit SmuTableTracker(int64_t guard_ns, int64_t hard_ns) : guard_ns_(guard_ns), hard_ns_(hard_ns) {}
+
+  // the source is polled back to back (Sampler::start_free) or not (everything else)
+  void set_back_to_back(bool on) {
+    if (on == on_) return;
+    on_ = on;
+    restart();
+  }
+  // forget the period (a failed read, another decoding path): acquire from scratch
+  void restart() {
+    state_ = on_ ? kAcquire : kOff;
+    agree_ = 0;
+    have_change_ = false;
+    prev_interval_ns_ = 0;
+    skipped_ = false;
+  }
+  // Read the table on the sample that starts at now_ns? (false: repeat the last table)
+  bool should_read(int64_t now_ns) {
+    if (state_ != kLocked) return true;
+    if (now_ns - last_read_ns_ >= hard_ns_ || now_ns >= change_ns_ + period_ns_ - guard_ns_) return true;
+    skipped_ = true;
+    return false;
+  }
+  // The outcome of the table read of the sample that started at now_ns: the table had
+  // `changed` since the previous read; fw_ts = its firmware timestamp (0: not known).
+  void record(int64_t now_ns, bool changed, uint64_t fw_ts = 0) {
+    last_read_ns_ = now_ns;
+    const bool first_after_skip = skipped_;
+    skipped_ = false;
+    if (state_ == kOff) return;
+    if (!changed) {
+      if (state_ == kLocked && now_ns > change_ns_ + period_ns_ + guard_ns_) resync();  // it did not come
+      return;
+    }
+    ++changes_;
+    const int64_t interval = now_ns - change_ns_;
+    const int64_t fw_interval = fw_ts != 0 && fw_ts_ != 0 && fw_ts > fw_ts_ ? int64_t(fw_ts - fw_ts_) * 10 : interval;
+    const bool had = have_change_;
+    have_change_ = true;
+    change_ns_ = now_ns;
+    fw_ts_ = fw_ts;
+    if (!had) return;
+    if (state_ == kLocked) {
+      if (2 * fw_interval > 3 * period_ns_) missed_ += uint64_t((fw_interval + period_ns_ / 2) / period_ns_ - 1);
+      if (first_after_skip || !agrees(interval, period_ns_)) return resync();
+      period_ns_ += (interval - period_ns_) / 8;
+      return;
+    }
+    // acquire: count consecutive intervals that agree with the one before
+    agree_ = (prev_interval_ns_ > 0 && agrees(interval, prev_interval_ns_)) ? agree_ + 1 : 1;
+    prev_interval_ns_ = interval;
+    if (agree_ >= kLockIntervals) {
+      state_ = kLocked;
+      period_ns_ = interval;
+      ++locks_;
+    }
+  }
+  State state() const { return state_; }
+  int64_t period_ns() const { return state_ == kLocked ? period_ns_ : 0; }
+  int64_t guard_ns() const { return guard_ns_; }
+  int64_t hard_ns() const { return hard_ns_; }
+  uint64_t changes() const { return changes_; }  // publications seen while tracking
+  uint64_t locks() const { return locks_; }
+  uint64_t resyncs() const { return resyncs_; }  // locked -> acquire
+  uint64_t missed() const { return missed_; }    // publications judged missed (interval > 1.5 P)
+
+ private:
+  bool agrees(int64_t a, int64_t b) const { return a - b <= guard_ns_ && b - a <= guard_ns_; }
+  void resync() {
+    ++resyncs_;
+    state_ = kAcquire;
+    agree_ = 0;
+    prev_interval_ns_ = 0;
+  }
+  int64_t guard_ns_, hard_ns_;
+  bool on_ = false, have_change_ = false, skipped_ = false;
+  State state_ = kOff;
+  int agree_ = 0;
+  int64_t period_ns_ = 0, prev_interval_ns_ = 0, change_ns_ = 0, last_read_ns_ = 0;
+  uint64_t fw_ts_ = 0;
+  uint64_t changes_ = 0, locks_ = 0, resyncs_ = 0, missed_ = 0;
+};
+// Guard and hard bound, from profiles/smu_track/publication_intervals.json (MI355X, 12 s
+// of back-to-back reads with the tracker off, 599 publication intervals): between the
+// detecting reads 19.81 .. 20.20 ms (p1 19.95, p99 20.05: one 46 us read of granularity);
+// the detection came -215 .. +194 us off the running period estimate above (p1 -57, p99
+// +45), the extremes being one late detection and the short interval after it. The guard
+// is about twice that extreme; the polled window then costs ~11 reads (0.5 ms) of every
+// 20 ms. The hard bound is 2.5 periods: it never fires on the measured cadence (largest
+// firmware-timestamp delta 21.0 ms) and keeps a wrongly locked table under 3 publications
+// stale.
+constexpr int64_t kSmuGuardNs = 500000;
+constexpr int64_t kSmuHardNs = 50000000;
 
 int amdsmi_gpu_count();                  // -1 if amd-smi cannot initialise
 std::vector<GpuInfo> amdsmi_enumerate();

@@ -143,6 +143,12 @@ __host__ __device__ constexpr int count_bits(int e) { return e <= 1 ? 1 : 1 + co
 // Free-running sampling brings 2 rows of the faster source into many refreshes: the
 // series with one row keep the one-row path, those with two take the general path at
 // 512 threads - hence `small_k`, the most entering rows that still count as few.
+// With the SMU table tracked (sources.h) the amd-smi ring brings 4-6 rows a refresh and
+// the launch is the 1024-thread one, the fifth and older rows pulled from the host ring.
+// `small_k` stays 2: with 8 (512 threads at that mix) the refresh's device part measured
+// 21.0-22.0 us against 20.4-20.5. Eight inline rows instead of kInlineRows = 4 (no pull
+// at that mix, a 2.4 KiB kernel argument) measured 20.1-20.7 against 20.2-20.9 us over
+// eight alternating rounds - no difference, not adopted (profiles/smu_track/).
 // Otherwise (first refresh, stateless): as many threads as the width, at most 1024.
 struct LaunchShape {
   int nt, e;
