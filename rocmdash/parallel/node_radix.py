@@ -93,7 +93,7 @@ def positions(nv: int, pct) -> tuple[list, list]:
     last = nv - 1 if nv else 0
     pos, frac = [], []
     for p in pct:
-        x = float(p) / 100.0 * float(last)
+        x = float(np.float32(p)) / 100.0 * float(last)  # the kernels take the percentile as a float
         lo = min(int(np.floor(x)), last)
         pos += [lo, lo + 1 if lo + 1 < nv else last]
         frac.append(float(np.float32(x - lo)))

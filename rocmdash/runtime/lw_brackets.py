@@ -66,7 +66,7 @@ def positions(nv: int, pct=PCT):
     last = nv - 1 if nv else 0
     out = []
     for p in pct:
-        x = float(p) / 100.0 * float(last)
+        x = float(np.float32(p)) / 100.0 * float(last)  # the kernels take the percentile as a float
         lo = min(int(np.floor(x)), last)
         out.append((lo, lo + 1 if lo + 1 < nv else last, float(np.float32(x - lo))))
     return out

@@ -6,9 +6,12 @@ wrap-around, host-ring overflow (lost rows become NaN), graph vs direct launches
 import numpy as np
 import pytest
 
-from rocmdash.ops.window_stats import window_stats_reference
+import _exact
+from rocmdash.ops.window_stats import DEFAULT_PCT, window_stats_reference
 
 pytestmark = pytest.mark.gpu
+
+LW_SUM_GROUP = _exact.long_window_sum_group()  # UG in csrc/long_window_pass.h
 
 
 def _rows(rng, k, width, base):
@@ -39,9 +42,18 @@ class _Mirror:
         return self.rows[-W:]
 
 
-def _check(out, mirrors, W):
+def _check(out, mirrors, W, final=True):
+    """``out``: one output or several of the same refresh. Against the fp64 reference, and -
+    on every refresh up to W = 65536, on the final one beyond (the sort of 12 x 2^20 samples
+    per refresh would dominate the test) - against the exact sorted-fp32 oracle."""
+    outs = [o.cpu().numpy() for o in (out if isinstance(out, (list, tuple)) else [out])]
     ref = np.concatenate([window_stats_reference(m.window(W).T) for m in mirrors])
-    np.testing.assert_allclose(out.cpu().numpy(), ref, rtol=1e-5, atol=1e-4)
+    for o in outs:
+        np.testing.assert_allclose(o, ref, rtol=1e-5, atol=1e-4)
+    if W <= 65536 or final:
+        ex = _exact.exact_stats(np.concatenate([m.window(W) for m in mirrors], axis=1), DEFAULT_PCT)
+        for o in outs:
+            assert _exact.assert_exact(o, ex, DEFAULT_PCT, sum_group=LW_SUM_GROUP) == 8 * len(ex.nv)
 
 
 @pytest.mark.parametrize("W", [1024, 65536, 1 << 20])
@@ -70,7 +82,7 @@ def test_long_window_matches_reference(native, cuda, W):
     steps = [min(cap, W // 3 + 5), 1, 0, 7, min(cap, W), 3, min(cap - 1, W + 11), 1]
     while sum(steps) < W + 3:
         steps.append(min(cap, W))
-    for k in steps:
+    for i, k in enumerate(steps):
         xa, xb = _rows(rng, k, 8, t), _rows(rng, k, 4, -t)
         ra.push_many(xa, np.arange(t, t + k, dtype=np.uint64))
         rb.push_many(xb, np.arange(t, t + k, dtype=np.uint64))
@@ -82,8 +94,7 @@ def test_long_window_matches_reference(native, cuda, W):
         lw_direct.refresh(out2.data_ptr(), stream)
         lw_small.refresh(out3.data_ptr(), stream)
         torch.cuda.synchronize()
-        _check(out, [ma, mb], W)
-        _check(out3, [ma, mb], W)
+        _check([out, out3], [ma, mb], W, final=i == len(steps) - 1)
         # graph and direct launches compute the same bits (fixed reduction order)
         assert torch.equal(out.nan_to_num(-7.0), out2.nan_to_num(-7.0))
         # other chunking: every order statistic identical
