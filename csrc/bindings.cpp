@@ -13,6 +13,7 @@
 #include "node_window.h"
 #include "publish.h"
 #include "rccl_comm.h"
+#include "window_buckets.h"
 
 namespace rocmdash {
 int launch_spin(uint32_t workgroups, double us, void* stream);  // calib.hip
@@ -461,6 +462,20 @@ PYBIND11_MODULE(_native, m) {
           },
           py::arg("dst_ptr"), py::arg("stream"),
           "Enqueue every series' resident sorted window as [S][1 + W] floats (count, samples, +inf).")
+      .def(
+          "export_buckets",
+          [](const DeviceWindowSet& w, uintptr_t bounds, uint32_t B, uintptr_t dst, uintptr_t stream) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_buckets(reinterpret_cast<const float*>(bounds), B, reinterpret_cast<float*>(dst),
+                                   reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_buckets failed: " + std::to_string(e));
+          },
+          py::arg("bounds_ptr"), py::arg("num_bounds"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue every series' cumulative le-buckets over its resident sorted window: bounds [S][B] -> "
+          "dst [S][B + 1] floats (samples <= each bound, then the valid count).")
       .def("stats", [](const DeviceWindowSet& w) {
         auto st = w.stats();
         py::dict d;
@@ -670,6 +685,25 @@ PYBIND11_MODULE(_native, m) {
       py::arg("node_ptr"), py::arg("n_ranks"), py::arg("num_series"), py::arg("window"), py::arg("out_ptr"),
       py::arg("stream"), py::arg("p0") = 50.f, py::arg("p1") = 90.f, py::arg("p2") = 99.f,
       "Order statistics over the union of N ranks' exported sorted windows: node [N][S][1 + W] -> out [S][8].");
+  m.attr("MAX_BUCKETS") = int(kMaxBuckets);
+  m.attr("BUCKET_SERIES_PER_LAUNCH") = int(kBucketSeriesPerLaunch);
+  m.def(
+      "bucket_blocks",
+      [](uintptr_t blocks, uint32_t N, uint32_t S, uint32_t W, uintptr_t bounds, uint32_t B, uintptr_t per_rank,
+         uintptr_t node, uintptr_t stream) {
+        int e;
+        {
+          py::gil_scoped_release nogil;
+          e = launch_bucket_blocks(reinterpret_cast<const float*>(blocks), N, S, W,
+                                   reinterpret_cast<const float*>(bounds), B, reinterpret_cast<float*>(per_rank),
+                                   reinterpret_cast<float*>(node), reinterpret_cast<void*>(stream));
+        }
+        if (e != 0) throw std::runtime_error("bucket_blocks failed: " + std::to_string(e));
+      },
+      py::arg("blocks_ptr"), py::arg("n_ranks"), py::arg("num_series"), py::arg("window"), py::arg("bounds_ptr"),
+      py::arg("num_bounds"), py::arg("per_rank_ptr"), py::arg("node_ptr"), py::arg("stream"),
+      "Cumulative le-buckets over export blocks [N][S][1 + W] and bounds [S][B]: per_rank [N][S][B + 1] and / or "
+      "node [S][B + 1] (the sum over the ranks); a pointer of 0 skips that output.");
 
   // ---- native frame renderer (csrc/frame_render.h) ---------------------------------
   py::class_<FramePlan, std::shared_ptr<FramePlan>>(m, "FramePlan")

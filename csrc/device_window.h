@@ -83,6 +83,12 @@ class DeviceWindowSet {
   // as [num_series][1 + W] floats (count, then ascending samples, +inf padding): the
   // per-rank block of the node-wide window statistics (node_window.h).
   void export_sorted(float* dst, void* stream) const;
+  // Enqueue, after the refresh that produced them, every series' cumulative le-buckets
+  // over its resident sorted window (window_buckets.h): bounds is device [num_series][B],
+  // finite and strictly ascending per series, dst device [num_series][B + 1] - the valid
+  // samples <= each bound, then the valid count (all zeros without state). 1 <= B <= 63.
+  // Returns a hipError_t (hipErrorInvalidValue before any launch for a bad argument).
+  int export_buckets(const float* bounds, uint32_t B, float* dst, void* stream) const;
   WindowSetStats stats() const { return st_; }
   // Tagged waits that found part of their refresh overwritten by a newer one (they
   // returned false and copied nothing usable: never a mix of two refreshes).

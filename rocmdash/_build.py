@@ -32,6 +32,7 @@ SOURCES = [
     "long_window_radix.hip",
     "long_window_brackets.hip",
     "node_window.hip",
+    "window_buckets.hip",
     "calib.hip",
     "publish.hip",
     "device_window.cpp",

@@ -26,6 +26,7 @@ from __future__ import annotations
 
 import argparse
 import logging
+import os
 import socket
 import threading
 import time
@@ -80,7 +81,11 @@ class SyntheticSource(SnapshotSource):
 class LocalNodeSource(SnapshotSource):
     """Every visible GPU in this process, background sampling, stats per scrape."""
 
-    def __init__(self, devices=None, source: str = "auto", counters: str = "auto", cfg=None):
+    def __init__(self, devices=None, source: str = "auto", counters: str = "auto", cfg=None,
+                 window_buckets: int | None = None):
+        """``window_buckets`` = B > 0 (default: ``ROCMDASH_WINDOW_BUCKETS``, else off): also
+        export every series' window as B cumulative le-buckets + ``+Inf``
+        (``rocmdash_window_bucket``; GpuAgent.window_buckets) and their sum over the GPUs."""
         from ..runtime import native
 
         native.load()
@@ -105,6 +110,10 @@ class LocalNodeSource(SnapshotSource):
         self.last_refresh_s = 0.0
         self.refresh_hist = LatencyHistogram("rocmdash_refresh_latency_seconds", "Device refresh latency per scrape")
         self._health = np.empty((len(self.agents), len(HEALTH_SOURCES), 8), dtype=np.float32)
+        if window_buckets is None:
+            window_buckets = int(os.environ.get("ROCMDASH_WINDOW_BUCKETS", "0") or 0)
+        # one set of bounds for the node (the first GPU's caps): buckets add up only over the same bounds
+        self.bucket_bounds = self.agents[0].default_bucket_bounds(int(window_buckets)) if window_buckets else None
 
     def collect(self):
         import torch
@@ -112,7 +121,12 @@ class LocalNodeSource(SnapshotSource):
         with self._lock:
             t0 = time.perf_counter()
             outs = [a.refresh() for a in self.agents]  # one launch per GPU, all async
+            buckets = None
+            if self.bucket_bounds is not None:  # in stream order behind each GPU's refresh
+                buckets = [a.window_buckets(self.bucket_bounds) for a in self.agents]
             host = np.stack([o.to("cpu", non_blocking=False).numpy() for o in outs])
+            if buckets is not None:
+                buckets = np.stack([b.to("cpu", non_blocking=False).numpy() for b in buckets])
             now_ns = time.time_ns()
             for i, a in enumerate(self.agents):
                 a.health_rows(self._health[i], now_ns)
@@ -136,6 +150,10 @@ class LocalNodeSource(SnapshotSource):
                                        [(a.info.smi_backend, a.info.counter_backend) for a in self.agents],
                                        self.agents[0].cfg.stale_periods),
         )
+        if buckets is not None:
+            snap.window_buckets = buckets
+            snap.window_bucket_bounds = self.bucket_bounds
+            snap.node_window_buckets = buckets.sum(axis=0, dtype=np.float64).astype(np.float32)
         exp = Exposition()
         for a, gid in zip(self.agents, ids):
             for sampler in a.samplers:
@@ -266,9 +284,13 @@ def main(argv=None) -> int:
     ap.add_argument("--synthetic", type=int, default=0, help="serve a synthetic node with N GPUs")
     ap.add_argument("--source", default="auto", choices=["auto", "hw", "synthetic"])
     ap.add_argument("--counters", default="auto", choices=["auto", "hw", "synthetic", "off"])
+    ap.add_argument("--window-buckets", type=int, default=None, metavar="B",
+                    help="also export every series' window as B cumulative le-buckets (1..63; default "
+                         "ROCMDASH_WINDOW_BUCKETS, else off)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
-    src = SyntheticSource(args.synthetic) if args.synthetic else LocalNodeSource(source=args.source, counters=args.counters)
+    src = SyntheticSource(args.synthetic) if args.synthetic else LocalNodeSource(
+        source=args.source, counters=args.counters, window_buckets=args.window_buckets)
     exp = Exporter(src)
     exp.serve(args.host, args.port)
     log.info("serving /metrics on %s:%d", args.host, exp.port)

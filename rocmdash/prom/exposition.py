@@ -137,7 +137,44 @@ def render_snapshot(snap, hostname: str = "", extra_labels: dict | None = None, 
                 lab["stat"] = sname
                 exp.add("rocmdash_node_window", snap.node_window[si, STAT_NAMES.index(sname)], lab,
                         "Window statistic of a series over every GPU's window at once (node-wide)")
+    render_window_buckets(exp, snap, hostname, extra)
     return exp.text()
+
+
+BUCKET_HELP = ("Valid samples of a series' last W samples that are <= le, cumulative (+Inf = all). A gauge, no counter "
+               "histogram: a window's distribution goes down as well as up. Sum by (le) before histogram_quantile")
+
+
+def bucket_le_labels(bounds) -> list:
+    """The ``le`` label values of one series' bounds, as ``utils.timing`` formats them."""
+    return [repr(float(b)) for b in bounds] + ["+Inf"]
+
+
+def render_window_buckets(exp: Exposition, snap, hostname: str = "", extra: dict | None = None) -> None:
+    """``rocmdash_window_bucket`` per GPU and ``rocmdash_node_window_bucket`` for their sum,
+    when the snapshot carries them (``NodeSnapshot.window_buckets`` and its neighbours)."""
+    bounds = getattr(snap, "window_bucket_bounds", None)
+    per_gpu = getattr(snap, "window_buckets", None)
+    node = getattr(snap, "node_window_buckets", None)
+    if bounds is None or not len(snap.window_series) or (per_gpu is None and node is None):
+        return
+    le = [bucket_le_labels(bounds[si]) for si in range(len(snap.window_series))]
+    if per_gpu is not None:
+        for g, gid in enumerate(snap.gpu_ids):
+            base = {"gpu_id": gid, "card_model": snap.card_models[g] or ""}
+            if hostname:
+                base["hostname"] = hostname
+            base.update(extra or {})
+            for si, series in enumerate(snap.window_series):
+                for b, lab_le in enumerate(le[si]):
+                    exp.add("rocmdash_window_bucket", per_gpu[g, si, b], dict(base, metric=series, le=lab_le), BUCKET_HELP)
+    if node is not None:
+        base = {"hostname": hostname} if hostname else {}
+        base.update(extra or {})
+        for si, series in enumerate(snap.window_series):
+            for b, lab_le in enumerate(le[si]):
+                exp.add("rocmdash_node_window_bucket", node[si, b], dict(base, metric=series, le=lab_le),
+                        BUCKET_HELP + " (every GPU's window of the node at once)")
 
 
 def render_health(exp: Exposition, health, gpu_ids, hostname: str = "", extra: dict | None = None) -> None:

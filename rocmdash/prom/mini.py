@@ -28,7 +28,7 @@ from dataclasses import dataclass, field
 from http.server import BaseHTTPRequestHandler, ThreadingHTTPServer
 
 from .exposition import format_value, parse_text
-from .promql import Aggregate, PromQLError, aggregate, parse
+from .promql import Aggregate, HistogramQuantile, PromQLError, aggregate, histogram_quantile, parse
 
 LOOKBACK_S = 300.0
 
@@ -243,7 +243,17 @@ class MiniPrometheus:
 
     def _evaluate(self, expr, at: float | None) -> dict:
         at = time.time() if at is None else at
-        if isinstance(expr, Aggregate):
+        if isinstance(expr, HistogramQuantile):
+            inner = expr.inner
+            if isinstance(inner, Aggregate):
+                rows = aggregate(inner, [(labels, v) for labels, v, _ in self.db.instant(inner.selector, at)])
+            else:
+                rows = [(labels, v) for labels, v, _ in self.db.instant(inner, at)]
+            res = [
+                {"metric": labels, "value": [at, format_value(v)]}
+                for labels, v in histogram_quantile(expr.phi, rows)
+            ]
+        elif isinstance(expr, Aggregate):
             rows = [(labels, v) for labels, v, _ in self.db.instant(expr.selector, at)]
             res = [
                 {"metric": labels, "value": [at, format_value(v)]}
@@ -259,7 +269,7 @@ class MiniPrometheus:
         series per GPU); aggregates go through ``query``."""
         expr = self._expr(q)  # parsed once; PromQLError for bad PromQL
         self.queries += 1
-        if isinstance(expr, Aggregate):
+        if isinstance(expr, (Aggregate, HistogramQuantile)):
             return json.dumps({"status": "success", "data": self._evaluate(expr, at)})
         res = self.db.instant_json(expr, at)
         return '{"status":"success","data":{"resultType":"vector","result":[' + ",".join(res) + "]}}"

@@ -9,6 +9,10 @@ K8s deployment's recording rules use:
     matcher    := label ('=' | '!=' | '=~' | '!~') string
     aggregate  := ('sum'|'avg'|'min'|'max'|'count') [('by'|'without') '(' labels ')']
                   '(' selector ')' [('by'|'without') '(' labels ')']
+    quantile   := 'histogram_quantile' '(' number ',' (selector | aggregate) ')'
+
+``histogram_quantile`` has Prometheus' semantics over cumulative ``le`` buckets (here the
+window distributions, ``rocmdash_window_bucket``): see :func:`bucket_quantile`.
 
 Regex matchers are fully anchored, as in Prometheus. A selector must contain at
 least one matcher that does not match the empty string (Prometheus' rule).
@@ -79,6 +83,12 @@ class Aggregate:
     selector: Selector
     by: tuple | None = None
     without: tuple | None = None
+
+
+@dataclass(frozen=True)
+class HistogramQuantile:
+    phi: float
+    inner: object  # Selector or Aggregate: the bucket series
 
 
 class _Lexer:
@@ -185,9 +195,11 @@ def _parse_grouping(lx: _Lexer):
     return None, None
 
 
-def parse(query: str):
-    """Parse a query into a ``Selector`` or an ``Aggregate``."""
-    lx = _Lexer(query.strip())
+_NUMBER = re.compile(r"[+-]?(?:[0-9]+\.?[0-9]*|\.[0-9]+)(?:[eE][+-]?[0-9]+)?|[+-]?(?:[iI]nf|NaN)")
+
+
+def _parse_vector(lx: _Lexer):
+    """A ``Selector`` or an ``Aggregate`` at the lexer's position."""
     save = lx.i
     word = lx.ident()
     if word in _AGGS:
@@ -197,14 +209,28 @@ def parse(query: str):
         lx.expect(")")
         if kw is None:
             kw, labels = _parse_grouping(lx)
-        if not lx.done():
-            raise PromQLError(f"unexpected trailing input at position {lx.i}")
         return Aggregate(word, sel, labels if kw == "by" else None, labels if kw == "without" else None)
     lx.i = save
-    sel = _parse_selector(lx)
+    return _parse_selector(lx)
+
+
+def parse(query: str):
+    """Parse a query into a ``Selector``, an ``Aggregate`` or a ``HistogramQuantile``."""
+    lx = _Lexer(query.strip())
+    save = lx.i
+    if lx.ident() == "histogram_quantile" and lx.eat("("):
+        num = lx.ident(_NUMBER)
+        if num is None:
+            raise PromQLError(f"expected the quantile (a number) at position {lx.i}")
+        lx.expect(",")
+        expr = HistogramQuantile(float(num), _parse_vector(lx))
+        lx.expect(")")
+    else:
+        lx.i = save
+        expr = _parse_vector(lx)
     if not lx.done():
         raise PromQLError(f"unexpected trailing input at position {lx.i}")
-    return sel
+    return expr
 
 
 def aggregate(expr: Aggregate, series: list) -> list:
@@ -234,3 +260,61 @@ def aggregate(expr: Aggregate, series: list) -> list:
             r = max(finite) if finite else float("nan")
         out.append((dict(key), r))
     return out
+
+
+def bucket_quantile(phi: float, buckets: list) -> float:
+    """Prometheus' ``histogram_quantile`` of one histogram: ``buckets`` [(le, cumulative
+    count)]. Buckets are sorted by ``le`` (equal bounds merged, counts made monotone); the
+    quantile is interpolated linearly inside its bucket, whose lower edge is the previous
+    bound - 0 for the first bucket when its bound is > 0 (a first bound <= 0 is returned as
+    it is). A quantile in the ``+Inf`` bucket gives the highest finite bound. NaN without a
+    ``+Inf`` bucket, without a finite one or without samples; -Inf / +Inf for phi < 0 / > 1."""
+    if math.isnan(phi):
+        return float("nan")
+    if phi < 0:
+        return float("-inf")
+    if phi > 1:
+        return float("inf")
+    bs = sorted((float(le), float(c)) for le, c in buckets if not math.isnan(float(le)))
+    if not bs or bs[-1][0] != float("inf"):
+        return float("nan")
+    merged = []
+    for le, c in bs:
+        if merged and merged[-1][0] == le:
+            merged[-1][1] += c
+        else:
+            merged.append([le, c])
+    for i in range(1, len(merged)):  # cumulative counts never go down
+        merged[i][1] = max(merged[i][1], merged[i - 1][1])
+    if len(merged) < 2:
+        return float("nan")
+    total = merged[-1][1]
+    if not total > 0:
+        return float("nan")
+    rank = phi * total
+    b = next((i for i in range(len(merged) - 1) if merged[i][1] >= rank), len(merged) - 1)
+    if b == len(merged) - 1:
+        return merged[-2][0]
+    if b == 0 and merged[0][0] <= 0:
+        return merged[0][0]
+    start, end, count = 0.0, merged[b][0], merged[b][1]
+    if b > 0:
+        start = merged[b - 1][0]
+        count -= merged[b - 1][1]
+        rank -= merged[b - 1][1]
+    return start + (end - start) * (rank / count)
+
+
+def histogram_quantile(phi: float, series: list) -> list:
+    """``series``: [(labels_dict, value)] of bucket series -> [(labels, quantile)], one per
+    group of all labels but ``le`` (and the metric name). Series without a parsable ``le``
+    are ignored, as Prometheus does."""
+    groups: dict = {}
+    for labels, v in series:
+        try:
+            le = float(labels["le"])
+        except (KeyError, ValueError):
+            continue
+        key = tuple(sorted((k, x) for k, x in labels.items() if k not in ("le", "__name__")))
+        groups.setdefault(key, []).append((le, v))
+    return [(dict(key), bucket_quantile(phi, b)) for key, b in groups.items()]

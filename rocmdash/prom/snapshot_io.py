@@ -37,6 +37,7 @@ from ..viz.panels import NodeSnapshot, natural_key
 VALUE_SERIES = COMPAT_METRICS + tuple(m for m in METRIC_SPECS if m not in COMPAT_METRICS)
 EXTENDED_SERIES = tuple(m for m in METRIC_SPECS if m not in COMPAT_METRICS)
 WINDOW_NAMES = ("rocmdash_window", "rocmdash_window_samples", "rocmdash_node_window")
+BUCKET_NAMES = ("rocmdash_window_bucket", "rocmdash_node_window_bucket")
 XCD_NAMES = ("amd_gpu_xcd_activity", "amd_gpu_xcd_gfx_clock")
 HEALTH_NAMES = ("rocmdash_sampler_samples_total", "rocmdash_sampler_failures_total", "rocmdash_sampler_overruns_total",
                 "rocmdash_sample_age_seconds", "rocmdash_sampler_rate_hz")
@@ -47,7 +48,7 @@ def extended_query(node_ip: str) -> str:
     """The one extra instant query of the extended view (everything the node service
     exports per GPU beyond the reference's five series), on the same instance filter
     as ``app.py:171``."""
-    names = EXTENDED_SERIES + ("amd_gpu_power_cap", "amd_gpu_info") + WINDOW_NAMES + XCD_NAMES + HEALTH_NAMES + (REFRESH_TS,)
+    names = EXTENDED_SERIES + ("amd_gpu_power_cap", "amd_gpu_info") + WINDOW_NAMES + BUCKET_NAMES + XCD_NAMES + HEALTH_NAMES + (REFRESH_TS,)
     return "{__name__=~\"" + "|".join(names) + "\", instance=~\"" + node_ip + ":.+\"}"
 
 
@@ -72,6 +73,8 @@ def snapshot_from_series(items, require_vram: bool = True) -> NodeSnapshot:
     backends: dict = {}  # gid -> {source: backend}
     names = set()
     refresh_time = None
+    buckets: dict = {}  # gid -> {(series, le): v}
+    node_buckets: dict = {}  # (series, le) -> v
     for labels, v in items:
         name = labels.get("__name__", "")
         v = float(v)
@@ -82,6 +85,16 @@ def snapshot_from_series(items, require_vram: bool = True) -> NodeSnapshot:
         if name == "rocmdash_node_window":
             key = (labels.get("metric", ""), labels.get("stat", ""))
             node_window[key] = v  # one series set per node; duplicates across ports: last wins
+            continue
+        if name in BUCKET_NAMES:
+            try:
+                key = (labels.get("metric", ""), float(labels.get("le", "")))
+            except ValueError:
+                continue
+            if name == "rocmdash_node_window_bucket":
+                node_buckets[key] = v
+            elif gid is not None:
+                _put(buckets, gid, key, v)
             continue
         if gid is None:
             continue
@@ -149,6 +162,8 @@ def snapshot_from_series(items, require_vram: bool = True) -> NodeSnapshot:
         snap.node_window = nw
         if not snap.window_series:
             snap.window_series = series
+    if node_buckets or buckets:
+        _fill_buckets(snap, buckets, node_buckets)
     if xcd:
         arr = np.full((len(gpu_ids), 2, XCDS), np.nan, dtype=np.float32)
         for gi, g in enumerate(gpu_ids):
@@ -174,6 +189,29 @@ def snapshot_from_series(items, require_vram: bool = True) -> NodeSnapshot:
         snap.source_health = SourceHealth(
             rows, [tuple(backends.get(g, {}).get(s, "") for s in HEALTH_SOURCES) for g in gpu_ids])
     return snap
+
+
+def _fill_buckets(snap: NodeSnapshot, per_gpu: dict, node: dict) -> None:
+    """The snapshot's bucket fields from ``{gid: {(series, le): count}}`` and the node's
+    ``{(series, le): count}``; left unset unless every series has the same number of bounds."""
+    keys = set(node)
+    for per in per_gpu.values():
+        keys |= set(per)
+    series = snap.window_series or tuple(c for c in VALUE_SERIES if any(s == c for s, _ in keys))
+    les = [sorted({le for s, le in keys if s == name}) for name in series]
+    if not series or len({len(x) for x in les}) != 1 or len(les[0]) < 2 or any(x[-1] != math.inf for x in les):
+        return
+    snap.window_bucket_bounds = np.array([x[:-1] for x in les], dtype=np.float32)
+    if not snap.window_series:
+        snap.window_series = series
+
+    def table(src):
+        return [[src.get((name, le), math.nan) for le in les[si]] for si, name in enumerate(series)]
+
+    if node:
+        snap.node_window_buckets = np.array(table(node), dtype=np.float32)
+    if per_gpu:
+        snap.window_buckets = np.array([table(per_gpu.get(g, {})) for g in snap.gpu_ids], dtype=np.float32)
 
 
 def merge_extended(base: NodeSnapshot, ext: NodeSnapshot) -> NodeSnapshot:
@@ -220,6 +258,12 @@ def merge_extended(base: NodeSnapshot, ext: NodeSnapshot) -> NodeSnapshot:
     snap.node_window = ext.node_window
     if ext.node_window is not None and not snap.window_series:
         snap.window_series = ext.window_series
+    if ext.window_bucket_bounds is not None:
+        snap.window_bucket_bounds, snap.node_window_buckets = ext.window_bucket_bounds, ext.node_window_buckets
+        if ext.window_buckets is not None:
+            b = ext.window_buckets[take].copy()
+            b[~present] = np.nan
+            snap.window_buckets = b
     if ext.xcd is not None:
         x = ext.xcd[take].copy()
         x[~present] = np.nan

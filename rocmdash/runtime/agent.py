@@ -527,6 +527,56 @@ class GpuAgent:
                 s += 1
         return torch.from_numpy(out)
 
+    def default_bucket_bounds(self, buckets: int = 16) -> np.ndarray:
+        """``[S, buckets]`` float32 upper bounds of this GPU's series: evenly spaced up to
+        each series' axis maximum, its own power cap and total VRAM where amd-smi reports
+        them (``rocmdash.ops.window_buckets.default_bounds``)."""
+        from ..ops.window_buckets import default_bounds
+
+        vram = self.smi_source.info().get("vram_total_mb")
+        return default_bounds(self.series, self.info.power_limit_w, float(vram) if vram else None, buckets,
+                              card_model=self.info.card_model)
+
+    def window_buckets(self, bounds=None):
+        """Every series' window as cumulative le-buckets, ``[S, B + 1]`` float32: the valid
+        window samples <= each of ``bounds`` ([S, B] or [B], finite, strictly ascending;
+        default ``default_bucket_bounds()``), then the valid count (``+Inf``). On a GPU the
+        counts come from the resident sorted windows the last ``refresh()`` left on the
+        device (csrc/window_buckets.hip), in stream order, into a buffer the next call
+        reuses; the bounds are uploaded once per bounds object."""
+        import torch
+
+        from ..ops.window_buckets import check_bounds, window_buckets_reference
+
+        if bounds is None:
+            bounds = getattr(self, "_default_bounds", None)
+            if bounds is None:
+                bounds = self._default_bounds = self.default_bucket_bounds()
+        S = len(self.series)
+        if self.dws is not None:
+            if not hasattr(self.dws, "export_buckets"):
+                raise ValueError("a window of > 32768 samples has no le-buckets: they are counted in the sorted "
+                                 "windows that only windows of <= 32768 samples keep resident (DeviceWindowSet)")
+            cached = getattr(self, "_bucket_bounds", None)
+            if cached is None or cached[0] is not bounds:
+                b = check_bounds(bounds, S)
+                dev = torch.from_numpy(b).to(self.device)
+                out = torch.empty((S, b.shape[1] + 1), dtype=torch.float32, device=self.device)
+                cached = self._bucket_bounds = (bounds, dev, out)
+            _, dev, out = cached
+            self.dws.export_buckets(dev.data_ptr(), dev.shape[1], out.data_ptr(), _current_raw_stream(self.device_index))
+            return out
+        b = check_bounds(bounds, S)
+        blocks = []
+        for r in self.rings:
+            rows, _ = r.window(self.window)
+            blocks.append(rows.T if len(rows) else np.full((r.width, 1), np.nan, dtype=np.float32))
+        out, s = np.empty((S, b.shape[1] + 1), dtype=np.float32), 0
+        for x in blocks:
+            out[s : s + len(x)] = window_buckets_reference(x, b[s : s + len(x)])
+            s += len(x)
+        return torch.from_numpy(out)
+
     def window_host(self, ring_index: int = 0):
         """Newest window of a ring on the host (oldest first) - for tests/debug."""
         return self.rings[ring_index].window(self.window)

@@ -209,10 +209,10 @@ def _export_sources(extra, pipe, gpu_ids) -> None:
                   "Rank 0's last raw SMU-table calibration result (text)")
 
 
-def refresh_node(pipe, agg, nws, latest, frame_out=None):
+def refresh_node(pipe, agg, nws, latest, frame_out=None, nbk=None):
     """One service refresh on every rank (collective). ONE gather carries every rank's
     stats, source health, per-XCD detail, footprint and stop vote (+ the node-window
-    gather with ``nws``); rank 0 hands the snapshot and the service's own metrics to
+    gather with ``nws``, + the small window-bucket gather with ``nbk``); rank 0 hands the snapshot and the service's own metrics to
     ``latest`` (the exporter's HTTP thread reads it) and optionally writes the frame.
     Returns every rank's stop vote. Raises when a collective fails (a rank is gone)."""
     from .prom.exposition import Exposition
@@ -221,6 +221,7 @@ def refresh_node(pipe, agg, nws, latest, frame_out=None):
     t0 = time.perf_counter()
     snap = pipe.latest_snapshot()
     node_stats = nws.refresh() if nws is not None else None  # collective too
+    buckets = nbk.refresh() if nbk is not None else None  # collective too (rocmdash.parallel.node_buckets)
     votes = pipe.stop_votes()
     t1 = time.perf_counter()
     wall1 = time.time()
@@ -243,6 +244,9 @@ def refresh_node(pipe, agg, nws, latest, frame_out=None):
         _export_self(extra, pipe, snap.gpu_ids)
         if node_stats is not None:
             snap.node_window = node_stats.cpu().numpy().astype("float64")
+        if buckets is not None:
+            snap.window_buckets, snap.node_window_buckets = buckets
+            snap.window_bucket_bounds = nbk.bounds
         latest.set(snap, extra)
         if frame_out:
             payload = render_frame_json(snap, snap.gpu_ids, extended=True)
@@ -272,7 +276,19 @@ def main(argv=None) -> int:
                     help="also export node-wide window statistics (all GPUs' windows, one extra all-gather)")
     ap.add_argument("--stall-seconds", type=float, default=0.0,
                     help="/healthz turns 503 after this long without a refresh (default: max(10 s, 5 periods))")
+    ap.add_argument("--window-buckets", type=int, default=0, metavar="B",
+                    help="also export every series' window as B cumulative le-buckets, per GPU and summed over the "
+                         "node (1..63; one extra all-gather of ~1 KB per rank; 0 = off)")
     args = ap.parse_args(argv)
+    if args.window_buckets:
+        from .config import SamplerConfig
+        from .ops.window_buckets import MAX_BUCKETS
+
+        if not 1 <= args.window_buckets <= MAX_BUCKETS:
+            ap.error(f"--window-buckets: 1 to {MAX_BUCKETS} buckets")
+        if SamplerConfig().long_window:
+            ap.error("--window-buckets needs a window of <= 32768 samples (ROCMDASH_WINDOW): buckets are counted in "
+                     "the resident sorted windows, which long windows do not keep")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(name)s %(message)s")
 
     from .parallel.membership import Membership
@@ -324,6 +340,12 @@ def main(argv=None) -> int:
         from .parallel.node_window import NodeWindowStats
 
         nws = NodeWindowStats(agent, agg, collective_timeout_s=args.collective_timeout)
+    nbk = None
+    if args.window_buckets:
+        from .parallel.node_buckets import NodeBuckets
+
+        nbk = NodeBuckets(agent, agg, agent.default_bucket_bounds(args.window_buckets),
+                          collective_timeout_s=args.collective_timeout)
     agent.start()
     log.info("rank %d: gather %s; footprint after start-up: %s; SCHED_IDLE: %s", env.rank, pipe.gather_report(),
              {k: {kk: vv for kk, vv in v.items() if vv is not None} for k, v in fp.stages.items()}, demoted)
@@ -349,7 +371,7 @@ def main(argv=None) -> int:
         # this rank's stop vote rides in its block of this refresh's gather
         pipe.stop_vote = 1.0 if (stop.is_set() or (args.max_refreshes and n + 1 >= args.max_refreshes)) else 0.0
         try:
-            votes = refresh_node(pipe, agg, nws, latest, frame_out=args.frame_out)
+            votes = refresh_node(pipe, agg, nws, latest, frame_out=args.frame_out, nbk=nbk)
             if n == 0:  # buffers the first refresh allocates (gather outputs, node window)
                 fp.mark("first_refresh")
         except Exception as e:  # a rank died or hung: leave for the launcher to restart the group
@@ -494,7 +516,7 @@ def main_supervised(args, mem) -> int:
         if got is None:
             break
         epoch, members = got
-        pipe = agg = nws = None
+        pipe = agg = nws = nbk = None
         try:
             _join_epoch(mem, epoch, members, args.collective_timeout)
             agg = NodeAggregator()
@@ -506,6 +528,11 @@ def main_supervised(args, mem) -> int:
                 from .parallel.node_window import NodeWindowStats
 
                 nws = NodeWindowStats(agent, agg, collective_timeout_s=args.collective_timeout)
+            if args.window_buckets:
+                from .parallel.node_buckets import NodeBuckets
+
+                nbk = NodeBuckets(agent, agg, agent.default_bucket_bounds(args.window_buckets),
+                                  collective_timeout_s=args.collective_timeout)
         except Exception as e:  # noqa: BLE001 - a member that never joined: reported, next epoch
             log.error("slot %d: joining epoch %d failed (%s)", slot, epoch, str(e).splitlines()[0] if str(e) else e)
             mem.report_failure(epoch, f"join: {e}")
@@ -524,7 +551,7 @@ def main_supervised(args, mem) -> int:
                 flags |= VOTE_REGROUP
             pipe.stop_vote = float(flags)
             try:
-                votes = refresh_node(pipe, agg, nws, latest, frame_out=args.frame_out)
+                votes = refresh_node(pipe, agg, nws, latest, frame_out=args.frame_out, nbk=nbk)
                 if n == 0:
                     fp.mark("first_refresh")
             except Exception as e:  # noqa: BLE001 - a member is gone or hung
@@ -548,7 +575,7 @@ def main_supervised(args, mem) -> int:
             else:
                 next_t = time.monotonic()
         _leave_epoch(pipe, agg)
-        nws = None
+        nws = nbk = None
     agent.close()
     pusher.close()
     if leaving or stop.is_set():

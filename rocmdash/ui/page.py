@@ -122,6 +122,29 @@ def node_window_table(snap: NodeSnapshot) -> dict | None:
             for i, series in enumerate(snap.window_series)}
 
 
+BUCKET_SHARES = (50, 75, 90)  # % of a series' axis (its highest finite bound)
+
+
+def window_bucket_table(snap: NodeSnapshot) -> dict | None:
+    """{series: {"> 50% of axis": share, ...}}: the share (%) of the node's window - every
+    GPU's last W samples - above 50 / 75 / 90 % of each series' axis, from the node's
+    le-buckets (``rocmdash.ops.window_buckets.share_above``; None if absent)."""
+    node = getattr(snap, "node_window_buckets", None)
+    bounds = getattr(snap, "window_bucket_bounds", None)
+    if node is None or bounds is None:
+        return None
+    from ..ops.window_buckets import share_above
+
+    table = {}
+    for i, series in enumerate(snap.window_series):
+        row = {"axis": float(bounds[i][-1]), "samples": int(node[i][-1])}
+        for pct in BUCKET_SHARES:
+            share = share_above(node[i], bounds[i], float(bounds[i][-1]) * pct / 100.0)
+            row[f"> {pct}% of axis (%)"] = round(100.0 * share, 2)
+        table[series] = row
+    return table
+
+
 def xcd_table(snap: NodeSnapshot, selected=None) -> dict | None:
     """{"GPU <id>": {"XCD <x> busy %": v, "XCD <x> MHz": v, ...}} of the selected GPUs'
     per-XCD detail (None if the data source has none)."""
@@ -144,7 +167,8 @@ def xcd_table(snap: NodeSnapshot, selected=None) -> dict | None:
     return table or None
 
 
-def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xcd: dict | None = None) -> None:
+def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xcd: dict | None = None,
+                  buckets: dict | None = None) -> None:
     st.subheader("Average Metrics (Selected GPUs)")
     avg_cols = st.columns(4)
     for col, (key, spec) in zip(avg_cols, frame.avg_panels):
@@ -172,6 +196,9 @@ def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xc
     if extended and node_window is not None:
         st.subheader("Node-wide Windowed Statistics (all GPUs)")
         st.dataframe(pd.DataFrame(node_window), use_container_width=True)
+    if extended and buckets is not None:
+        st.subheader("Node-wide Window Distribution (share of samples above 50 / 75 / 90 % of the axis)")
+        st.dataframe(pd.DataFrame.from_dict(buckets, orient="index"), use_container_width=True)
     if extended and xcd is not None:
         st.subheader("Per-XCD Activity and Clocks")
         st.dataframe(pd.DataFrame.from_dict(xcd, orient="index"), use_container_width=True)
@@ -240,7 +267,8 @@ def main(max_refreshes: int | None = None, data_source: str | None = None) -> No
                     snap, st.session_state.selected_gpus, use_gauge=st.session_state.use_gauge, extended=extended, now=now
                 )
                 _render_frame(st, frame, extended, node_window_table(snap) if extended else None,
-                              xcd_table(snap, st.session_state.selected_gpus) if extended else None)
+                              xcd_table(snap, st.session_state.selected_gpus) if extended else None,
+                              window_bucket_table(snap) if extended else None)
         n += 1
         if max_refreshes is not None and n >= max_refreshes:
             break

@@ -99,6 +99,13 @@ class NodeSnapshot:
     # rocmdash_node_refresh_timestamp_seconds), when the data source exports it: a
     # sample's own time is refresh_time - its source's age_s
     refresh_time: float | None = None
+    # Window distributions as cumulative le-buckets (rocmdash.ops.window_buckets), when
+    # computed: per GPU [N, S, B + 1] - the valid window samples <= each bound of
+    # window_bucket_bounds [S, B], then the valid count (+Inf) - and their sum over the
+    # GPUs [S, B + 1], the node's window
+    window_buckets: np.ndarray | None = None
+    window_bucket_bounds: np.ndarray | None = None
+    node_window_buckets: np.ndarray | None = None
 
     def __post_init__(self):
         self.values = np.asarray(self.values, dtype=np.float64)
