@@ -14,6 +14,7 @@
 #include "publish.h"
 #include "rccl_comm.h"
 #include "window_buckets.h"
+#include "window_trend.h"
 
 namespace rocmdash {
 int launch_spin(uint32_t workgroups, double us, void* stream);  // calib.hip
@@ -364,6 +365,19 @@ PYBIND11_MODULE(_native, m) {
           },
           py::arg("out_ptr"), py::arg("stream"), py::arg("p0") = 50.0f, py::arg("p1") = 90.0f, py::arg("p2") = 99.0f)
       .def(
+          "export_trend",
+          [](LongWindowSet& w, uint32_t P, uintptr_t dst, uintptr_t stream) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_trend(P, reinterpret_cast<float*>(dst), reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_trend failed: " + std::to_string(e));
+          },
+          py::arg("columns"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue every series' window trend after the last refresh: dst [S][columns + 1][4] floats "
+          "(min, max, mean, count per slot of window / columns rows).")
+      .def(
           "refresh_node",
           [](LongWindowSet& w, uintptr_t out, uintptr_t stream, float p0, float p1, float p2,
              std::shared_ptr<RcclComm> comm, bool timing, double timeout_s, py::object abandon) {
@@ -476,6 +490,19 @@ PYBIND11_MODULE(_native, m) {
           py::arg("bounds_ptr"), py::arg("num_bounds"), py::arg("dst_ptr"), py::arg("stream"),
           "Enqueue every series' cumulative le-buckets over its resident sorted window: bounds [S][B] -> "
           "dst [S][B + 1] floats (samples <= each bound, then the valid count).")
+      .def(
+          "export_trend",
+          [](const DeviceWindowSet& w, uint32_t P, uintptr_t dst, uintptr_t stream) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_trend(P, reinterpret_cast<float*>(dst), reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_trend failed: " + std::to_string(e));
+          },
+          py::arg("columns"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue every series' window trend after the last refresh: dst [S][columns + 1][4] floats "
+          "(min, max, mean, count per slot of window / columns rows).")
       .def("stats", [](const DeviceWindowSet& w) {
         auto st = w.stats();
         py::dict d;
@@ -704,6 +731,24 @@ PYBIND11_MODULE(_native, m) {
       py::arg("num_bounds"), py::arg("per_rank_ptr"), py::arg("node_ptr"), py::arg("stream"),
       "Cumulative le-buckets over export blocks [N][S][1 + W] and bounds [S][B]: per_rank [N][S][B + 1] and / or "
       "node [S][B + 1] (the sum over the ranks); a pointer of 0 skips that output.");
+  m.attr("MAX_TREND_COLUMNS") = int(kMaxTrendColumns);
+  m.attr("MAX_TREND_ROWS_PER_COLUMN") = int(kMaxTrendRowsPerColumn);
+  m.def(
+      "trend_ring",
+      [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n, uint32_t P,
+         uint32_t rows_per_col, uintptr_t dst, uintptr_t stream) {
+        int e;
+        {
+          py::gil_scoped_release nogil;
+          e = launch_trend_ring(reinterpret_cast<const float*>(base), stride, cols, depth, head, n, P, rows_per_col,
+                                reinterpret_cast<float*>(dst), reinterpret_cast<void*>(stream));
+        }
+        if (e != 0) throw std::runtime_error("trend_ring failed: " + std::to_string(e));
+      },
+      py::arg("base_ptr"), py::arg("stride"), py::arg("cols"), py::arg("depth"), py::arg("head"), py::arg("n"),
+      py::arg("columns"), py::arg("rows_per_col"), py::arg("dst_ptr"), py::arg("stream"),
+      "Window trend of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) whose window is rows "
+      "[head - n, head): dst [cols][columns + 1][4] floats (min, max, mean, count per slot of rows_per_col rows).");
 
   // ---- native frame renderer (csrc/frame_render.h) ---------------------------------
   py::class_<FramePlan, std::shared_ptr<FramePlan>>(m, "FramePlan")

@@ -89,6 +89,13 @@ class DeviceWindowSet {
   // samples <= each bound, then the valid count (all zeros without state). 1 <= B <= 63.
   // Returns a hipError_t (hipErrorInvalidValue before any launch for a bad argument).
   int export_buckets(const float* bounds, uint32_t B, float* dst, void* stream) const;
+  // Enqueue, after the refresh that produced it, every series' window trend
+  // (window_trend.h): the window of the last refresh cut into P + 1 slots of window / P rows,
+  // anchored to absolute row numbers; dst device [num_series][P + 1][4] = {min, max, mean,
+  // count} (count 0 and NaNs for an empty slot; every slot before the first refresh and
+  // after invalidate()). P a power of two in [8, 1024], <= window. Returns a hipError_t
+  // (hipErrorInvalidValue before any launch for a bad argument).
+  int export_trend(uint32_t P, float* dst, void* stream) const;
   WindowSetStats stats() const { return st_; }
   // Tagged waits that found part of their refresh overwritten by a newer one (they
   // returned false and copied nothing usable: never a mix of two refreshes).

@@ -243,6 +243,14 @@ class LongWindowSet {
   std::vector<std::array<uint32_t, 18>> bracket_state(int mode = 0) const;
   // Enqueue new-row copies + the statistics passes on `stream`; out = device [S][8].
   void refresh(float* out, void* stream, float p0, float p1, float p2);
+  // Enqueue, after the refresh that left it on the device, every series' window trend
+  // (window_trend.h, defined in window_trend.hip): dst device [num_series][P + 1][4] =
+  // {min, max, mean, count} per slot of window / P rows (<= 65536: 2^24 needs P >= 256).
+  // Rows the host ring lost count as invalid, as in the statistics. Returns a hipError_t:
+  // hipErrorInvalidValue before any launch for a bad argument, hipErrorNotReady while rows
+  // are staged that no kernel has written yet (between stage() and its flush: never after
+  // refresh()).
+  int export_trend(uint32_t P, float* dst, void* stream);
   // Node-wide statistics over the union of every rank's window (collective: every rank
   // of `comm` calls it with the same series layout): the same passes as refresh(), with
   // the ranks' pass-0 predictions and partials all-gathered and every digit histogram

@@ -25,6 +25,7 @@ overruns, last sample age (staleness), scrape and refresh durations.
 from __future__ import annotations
 
 import argparse
+import json
 import logging
 import os
 import socket
@@ -82,12 +83,23 @@ class LocalNodeSource(SnapshotSource):
     """Every visible GPU in this process, background sampling, stats per scrape."""
 
     def __init__(self, devices=None, source: str = "auto", counters: str = "auto", cfg=None,
-                 window_buckets: int | None = None):
+                 window_buckets: int | None = None, window_trend: int | None = None):
         """``window_buckets`` = B > 0 (default: ``ROCMDASH_WINDOW_BUCKETS``, else off): also
         export every series' window as B cumulative le-buckets + ``+Inf``
-        (``rocmdash_window_bucket``; GpuAgent.window_buckets) and their sum over the GPUs."""
+        (``rocmdash_window_bucket``; GpuAgent.window_buckets) and their sum over the GPUs.
+        ``window_trend`` = P > 0 (default: ``ROCMDASH_WINDOW_TREND``, else off): the snapshot
+        also carries every series' window as P + 1 columns of {min, max, mean, count}
+        (GpuAgent.window_trend), served as JSON by ``GET /trend`` - never in ``/metrics``."""
         from ..runtime import native
 
+        if window_trend is None:
+            window_trend = int(os.environ.get("ROCMDASH_WINDOW_TREND", "0") or 0)
+        self.trend_columns = int(window_trend) if window_trend else None
+        if self.trend_columns is not None:  # checked before any agent starts its samplers
+            from ..config import SamplerConfig
+            from ..ops.window_trend import check_columns
+
+            check_columns(self.trend_columns, (cfg or SamplerConfig()).window)
         native.load()
         if counters in ("auto", "hw"):
             native.enable_counters()
@@ -124,9 +136,15 @@ class LocalNodeSource(SnapshotSource):
             buckets = None
             if self.bucket_bounds is not None:  # in stream order behind each GPU's refresh
                 buckets = [a.window_buckets(self.bucket_bounds) for a in self.agents]
+            trend = age = None
+            if self.trend_columns is not None:  # likewise: the rings as this refresh left them
+                trend = [a.window_trend(self.trend_columns) for a in self.agents]
+                age = self.agents[0].trend_age_rows(self.trend_columns)
             host = np.stack([o.to("cpu", non_blocking=False).numpy() for o in outs])
             if buckets is not None:
                 buckets = np.stack([b.to("cpu", non_blocking=False).numpy() for b in buckets])
+            if trend is not None:
+                trend = np.stack([t.to("cpu", non_blocking=False).numpy() for t in trend])
             now_ns = time.time_ns()
             for i, a in enumerate(self.agents):
                 a.health_rows(self._health[i], now_ns)
@@ -154,6 +172,8 @@ class LocalNodeSource(SnapshotSource):
             snap.window_buckets = buckets
             snap.window_bucket_bounds = self.bucket_bounds
             snap.node_window_buckets = buckets.sum(axis=0, dtype=np.float64).astype(np.float32)
+        if trend is not None:
+            snap.window_trend, snap.window_trend_age_rows = trend, age
         exp = Exposition()
         for a, gid in zip(self.agents, ids):
             for sampler in a.samplers:
@@ -162,7 +182,8 @@ class LocalNodeSource(SnapshotSource):
                         "Mean duration of one source read")
         exp.add("rocmdash_refresh_seconds", self.last_refresh_s, {}, "Device refresh (stats kernel + D2H) of the last scrape")
         self.refresh_hist.add_to(exp)
-        torch.cuda.synchronize()
+        if any(a.use_gpu for a in self.agents):
+            torch.cuda.synchronize()
         return snap, exp
 
     def close(self) -> None:
@@ -180,6 +201,30 @@ class PipelineSource(SnapshotSource):
     def collect(self):
         with self._lock:
             return self.pipeline.latest_snapshot(), None
+
+
+def _nullable(x) -> list:
+    """A float array as a JSON-ready list: NaN becomes None (JSON has no NaN)."""
+    return [None if v != v else float(v) for v in np.asarray(x, dtype=np.float64).ravel()]
+
+
+def render_trend(snap: NodeSnapshot) -> str | None:
+    """The snapshot's window trend as the ``/trend`` document, None when it carries none:
+    ``{"columns": P, "age_rows": [P + 1], "series": [...], "gpus": {gpu_id: {metric: {"min":
+    [P + 1], "max": ..., "mean": ..., "count": ...}}}}``, slot 0 the oldest, empty slots null."""
+    trend = getattr(snap, "window_trend", None)
+    if trend is None:
+        return None
+    trend = np.asarray(trend)
+    series = list(snap.window_series)
+    gpus = {}
+    for g, gid in enumerate(snap.gpu_ids):
+        gpus[gid] = {m: {k: _nullable(trend[g, s, :, i]) for i, k in enumerate(("min", "max", "mean", "count"))}
+                     for s, m in enumerate(series)}
+    age = snap.window_trend_age_rows
+    doc = {"columns": int(trend.shape[2]) - 1, "age_rows": _nullable(age) if age is not None else None,
+           "series": series, "gpus": gpus}
+    return json.dumps(doc, allow_nan=False)
 
 
 class Exporter:
@@ -218,6 +263,17 @@ class Exporter:
         own.add("rocmdash_exporter_scrape_seconds", self.last_scrape_s, {}, "Duration of the last collection")
         return body + own.text()
 
+    def trend(self) -> str | None:
+        """The ``/trend`` document of a fresh collection; None when the source has no window
+        trend (the option is off) or the collection failed."""
+        try:
+            snap, _ = self.source.collect()
+            return render_trend(snap)
+        except Exception:
+            self.errors += 1
+            log.exception("collect failed")
+            return None
+
     def health(self) -> tuple:
         """(ok, message) for /healthz: the source's own verdict when it has one (the
         node service reports unhealthy when its refresh loop stalls), else OK."""
@@ -246,6 +302,12 @@ class Exporter:
                     body = exporter.render().encode()
                     ctype = CONTENT_TYPE
                     code = 200
+                elif self.path.split("?")[0] == "/trend":
+                    doc = exporter.trend()
+                    if doc is None:
+                        body, ctype, code = b"no window trend (start with --window-trend P)\n", "text/plain", 404
+                    else:
+                        body, ctype, code = doc.encode(), "application/json", 200
                 elif self.path in ("/healthz", "/-/healthy"):
                     ok, msg = exporter.health()
                     body, ctype, code = (msg + "\n").encode(), "text/plain", 200 if ok else 503
@@ -287,10 +349,13 @@ def main(argv=None) -> int:
     ap.add_argument("--window-buckets", type=int, default=None, metavar="B",
                     help="also export every series' window as B cumulative le-buckets (1..63; default "
                          "ROCMDASH_WINDOW_BUCKETS, else off)")
+    ap.add_argument("--window-trend", type=int, default=None, metavar="P",
+                    help="also serve GET /trend: every series' window as P + 1 columns of min / max / mean / count "
+                         "(a power of two in 8..1024; default ROCMDASH_WINDOW_TREND, else off)")
     args = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO)
     src = SyntheticSource(args.synthetic) if args.synthetic else LocalNodeSource(
-        source=args.source, counters=args.counters, window_buckets=args.window_buckets)
+        source=args.source, counters=args.counters, window_buckets=args.window_buckets, window_trend=args.window_trend)
     exp = Exporter(src)
     exp.serve(args.host, args.port)
     log.info("serving /metrics on %s:%d", args.host, exp.port)

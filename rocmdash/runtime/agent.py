@@ -577,6 +577,46 @@ class GpuAgent:
             s += len(x)
         return torch.from_numpy(out)
 
+    def window_trend(self, columns: int = 128):
+        """Every series' window as a line over time, ``[S, columns + 1, 4]`` float32: per
+        slot of ``window / columns`` rows ``{min, max, mean, count}``, slot 0 the oldest
+        (``rocmdash.ops.window_trend``; ``trend_age_rows`` gives the x axis). On a GPU the
+        slots are reduced from the device rings the last ``refresh()`` left there
+        (csrc/window_trend.hip), short or long windows alike, in stream order, into a buffer
+        the next call with the same ``columns`` reuses."""
+        import torch
+
+        from ..ops.window_trend import check_columns, window_trend_reference
+
+        P = int(columns)
+        check_columns(P, self.window)
+        S = len(self.series)
+        if self.dws is not None:
+            cached = getattr(self, "_trend_out", None)
+            if cached is None or cached.shape[1] != P + 1:
+                cached = self._trend_out = torch.empty((S, P + 1, 4), dtype=torch.float32, device=self.device)
+            self.dws.export_trend(P, cached.data_ptr(), _current_raw_stream(self.device_index))
+            return cached
+        out, s = np.empty((S, P + 1, 4), dtype=np.float32), 0
+        for r in self.rings:
+            for _ in range(8):  # the window and the head it ends at, with no row pushed in between
+                head = int(r.head)
+                rows, _ = r.window(self.window)
+                if int(r.head) == head:
+                    break
+            rows = np.asarray(rows, dtype=np.float32).reshape(-1, r.width)
+            out[s : s + r.width] = window_trend_reference(rows, head, self.window, P)
+            s += r.width
+        return torch.from_numpy(out)
+
+    def trend_age_rows(self, columns: int = 128, ring_index: int = 0) -> np.ndarray:
+        """``[columns + 1]``: rows between each trend slot's last row and the newest row of
+        ring ``ring_index`` (NaN: an empty slot), from the ring's head now."""
+        from ..ops.window_trend import trend_age_rows
+
+        h = int(self.rings[ring_index].head)
+        return trend_age_rows(h, min(h, self.window), self.window, int(columns))
+
     def window_host(self, ring_index: int = 0):
         """Newest window of a ring on the host (oldest first) - for tests/debug."""
         return self.rings[ring_index].window(self.window)

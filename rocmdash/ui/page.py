@@ -145,6 +145,40 @@ def window_bucket_table(snap: NodeSnapshot) -> dict | None:
     return table
 
 
+def window_trend_figures(snap: NodeSnapshot, selected=None, height: int = 220) -> list | None:
+    """[(key, Figure)]: per selected GPU the window trend (``rocmdash.ops.window_trend``) of
+    every panel metric the snapshot's trend has - utilisation, temperature, power and the
+    extended panels - as a min..max band and a mean line over seconds (None if the snapshot
+    carries no trend). The slots' ages are rows of the first ring; a series' seconds are
+    those rows times its own source's period (amd-smi or device counters)."""
+    trend = getattr(snap, "window_trend", None)
+    age = getattr(snap, "window_trend_age_rows", None)
+    if trend is None or age is None:
+        return None
+    from ..models.schema import CTR_FIELDS
+    from ..viz.figures import create_trend
+    from ..viz.panels import EXTENDED_PANELS, POWER, TEMP, UTIL
+
+    cfg = config.SamplerConfig()
+    index = {s: i for i, s in enumerate(snap.window_series)}
+    sel = set(str(g) for g in selected) if selected is not None else None
+    figs = []
+    for g, gid in enumerate(snap.gpu_ids):
+        if sel is not None and gid not in sel:
+            continue
+        panels = [(UTIL, "GPU Utilization (%)", "gpu_util", 100.0), (TEMP, "Temperature (°C)", "temp", 100.0),
+                  (POWER, "Power Usage (W)", "power", snap.power_max(gid))] + list(EXTENDED_PANELS)
+        for col, title, key, mx in panels:
+            s = index.get(col)
+            if s is None:
+                continue
+            period = 1.0 / (cfg.counter_hz if col in CTR_FIELDS else cfg.smi_hz)
+            t = trend[g, s]
+            figs.append((f"plot_trend_{key}_{gid}_", create_trend(f"GPU {gid}: {title}", [a * period for a in age],
+                                                                   t[:, 0], t[:, 1], t[:, 2], mx, height)))
+    return figs
+
+
 def xcd_table(snap: NodeSnapshot, selected=None) -> dict | None:
     """{"GPU <id>": {"XCD <x> busy %": v, "XCD <x> MHz": v, ...}} of the selected GPUs'
     per-XCD detail (None if the data source has none)."""
@@ -168,7 +202,7 @@ def xcd_table(snap: NodeSnapshot, selected=None) -> dict | None:
 
 
 def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xcd: dict | None = None,
-                  buckets: dict | None = None) -> None:
+                  buckets: dict | None = None, trend: list | None = None) -> None:
     st.subheader("Average Metrics (Selected GPUs)")
     avg_cols = st.columns(4)
     for col, (key, spec) in zip(avg_cols, frame.avg_panels):
@@ -199,6 +233,12 @@ def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xc
     if extended and buckets is not None:
         st.subheader("Node-wide Window Distribution (share of samples above 50 / 75 / 90 % of the axis)")
         st.dataframe(pd.DataFrame.from_dict(buckets, orient="index"), use_container_width=True)
+    if extended and trend:
+        st.subheader("Window Trend (min / max band and mean per column of the window)")
+        for i in range(0, len(trend), 4):
+            for col, (key, fig) in zip(st.columns(4), trend[i : i + 4]):
+                with col:
+                    st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
     if extended and xcd is not None:
         st.subheader("Per-XCD Activity and Clocks")
         st.dataframe(pd.DataFrame.from_dict(xcd, orient="index"), use_container_width=True)
@@ -268,7 +308,8 @@ def main(max_refreshes: int | None = None, data_source: str | None = None) -> No
                 )
                 _render_frame(st, frame, extended, node_window_table(snap) if extended else None,
                               xcd_table(snap, st.session_state.selected_gpus) if extended else None,
-                              window_bucket_table(snap) if extended else None)
+                              window_bucket_table(snap) if extended else None,
+                              window_trend_figures(snap, st.session_state.selected_gpus) if extended else None)
         n += 1
         if max_refreshes is not None and n >= max_refreshes:
             break

@@ -401,6 +401,45 @@ def spec_json_parts(spec) -> tuple:
     return head, get_color_for_value(value, max_val), mid, _value_json(value), tail
 
 
+TREND_LINE = "#2980b9"
+TREND_BAND = "rgba(41,128,185,0.25)"
+
+
+def create_trend(title, age_s, lo, hi, mean, max_val=None, height=220) -> Figure:
+    """A window trend (``rocmdash.ops.window_trend``) as a line over time: the slots'
+    min..max as a band, their mean as a line, x = seconds before the newest sample
+    (negative: time runs left to right). ``age_s`` / ``lo`` / ``hi`` / ``mean`` hold one
+    entry per slot, oldest first; a slot whose age or mean is NaN (empty: no valid sample)
+    becomes a null point in all three traces - a gap, never a line drawn across it.
+    ``max_val``: the top of the y axis (None: autorange). No reference counterpart."""
+    xs, ys = [], ([], [], [])
+    for a, *v in zip(age_s, lo, hi, mean):
+        a, v = _num(a), [_num(x) for x in v]
+        gap = a is None or v[2] is None
+        xs.append(None if a is None else -a)
+        for y, x in zip(ys, v):
+            y.append(None if gap else x)
+
+    def trace(name, y, line, **more):
+        return {"line": line, "mode": "lines", "name": name, "x": list(xs), "y": y, "type": "scatter", **more}
+
+    data = [
+        trace("min", ys[0], {"width": 0}, hoverinfo="skip"),
+        trace("max", ys[1], {"width": 0}, fill="tonexty", fillcolor=TREND_BAND, hoverinfo="skip"),
+        trace("mean", ys[2], {"color": TREND_LINE, "width": 2}),
+    ]
+    yaxis = {"range": [0, _num(max_val)]} if max_val is not None and _num(max_val) else {}
+    layout = {
+        "title": {"text": title},
+        "xaxis": {"title": {"text": "seconds"}, "showgrid": True, "gridcolor": "lightgray"},
+        "yaxis": yaxis,
+        "margin": {"l": 40, "r": 20, "t": 40, "b": 40},
+        "height": _num(height),
+        "showlegend": False,
+    }
+    return Figure(data, layout)
+
+
 def create_chart(value, title, max_val, height, use_gauge=True) -> Figure:
     """Style dispatch without any UI-framework state (the app layer supplies
     ``use_gauge`` from the session, app.py:242-245)."""

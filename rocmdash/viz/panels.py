@@ -106,6 +106,12 @@ class NodeSnapshot:
     window_buckets: np.ndarray | None = None
     window_bucket_bounds: np.ndarray | None = None
     node_window_buckets: np.ndarray | None = None
+    # Window trend (rocmdash.ops.window_trend), when computed: per GPU [N, S, P + 1, 4] -
+    # {min, max, mean, count} of each of the window's P + 1 column slots, slot 0 the oldest
+    # - and [P + 1] how many rows before the newest each slot ends (NaN: empty), counted in
+    # the first ring's rows (another ring's newest column differs by less than one column)
+    window_trend: np.ndarray | None = None
+    window_trend_age_rows: np.ndarray | None = None
 
     def __post_init__(self):
         self.values = np.asarray(self.values, dtype=np.float64)
