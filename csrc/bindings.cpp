@@ -13,6 +13,7 @@
 #include "node_window.h"
 #include "publish.h"
 #include "rccl_comm.h"
+#include "long_window_buckets.h"
 #include "window_buckets.h"
 #include "window_trend.h"
 
@@ -378,6 +379,20 @@ PYBIND11_MODULE(_native, m) {
           "Enqueue every series' window trend after the last refresh: dst [S][columns + 1][4] floats "
           "(min, max, mean, count per slot of window / columns rows).")
       .def(
+          "export_buckets",
+          [](LongWindowSet& w, uintptr_t bounds, uint32_t B, uintptr_t dst, uintptr_t stream) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_buckets(reinterpret_cast<const float*>(bounds), B, reinterpret_cast<double*>(dst),
+                                   reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_buckets failed: " + std::to_string(e));
+          },
+          py::arg("bounds_ptr"), py::arg("num_bounds"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue every series' cumulative le-buckets over the window of the last refresh, streamed from the "
+          "device rings: bounds [S][B] floats -> dst [S][B + 1] doubles (samples <= each bound, then the valid count).")
+      .def(
           "refresh_node",
           [](LongWindowSet& w, uintptr_t out, uintptr_t stream, float p0, float p1, float p2,
              std::shared_ptr<RcclComm> comm, bool timing, double timeout_s, py::object abandon) {
@@ -731,6 +746,23 @@ PYBIND11_MODULE(_native, m) {
       py::arg("num_bounds"), py::arg("per_rank_ptr"), py::arg("node_ptr"), py::arg("stream"),
       "Cumulative le-buckets over export blocks [N][S][1 + W] and bounds [S][B]: per_rank [N][S][B + 1] and / or "
       "node [S][B + 1] (the sum over the ranks); a pointer of 0 skips that output.");
+  m.def(
+      "bucket_ring",
+      [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n, uintptr_t bounds,
+         uint32_t B, uintptr_t dst, uintptr_t stream) {
+        int e;
+        {
+          py::gil_scoped_release nogil;
+          e = launch_bucket_ring(reinterpret_cast<const float*>(base), stride, cols, depth, head, n,
+                                 reinterpret_cast<const float*>(bounds), B, reinterpret_cast<double*>(dst),
+                                 reinterpret_cast<void*>(stream));
+        }
+        if (e != 0) throw std::runtime_error("bucket_ring failed: " + std::to_string(e));
+      },
+      py::arg("base_ptr"), py::arg("stride"), py::arg("cols"), py::arg("depth"), py::arg("head"), py::arg("n"),
+      py::arg("bounds_ptr"), py::arg("num_bounds"), py::arg("dst_ptr"), py::arg("stream"),
+      "Cumulative le-buckets of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) whose window is "
+      "rows [head - n, head): bounds [cols][B] floats -> dst [cols][B + 1] doubles.");
   m.attr("MAX_TREND_COLUMNS") = int(kMaxTrendColumns);
   m.attr("MAX_TREND_ROWS_PER_COLUMN") = int(kMaxTrendRowsPerColumn);
   m.def(

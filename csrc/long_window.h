@@ -251,6 +251,13 @@ class LongWindowSet {
   // are staged that no kernel has written yet (between stage() and its flush: never after
   // refresh()).
   int export_trend(uint32_t P, float* dst, void* stream);
+  // Enqueue, after the refresh that left it on the device, every series' cumulative
+  // le-buckets (long_window_buckets.h, defined in long_window_buckets.hip): bounds device
+  // [num_series][B], dst device [num_series][B + 1] doubles, series in set order. One
+  // stream over the rings per call; rows the host ring lost count as invalid. Returns a
+  // hipError_t as export_trend does: hipErrorInvalidValue before any launch or write for a
+  // bad argument, hipErrorNotReady while rows are staged that no kernel has written yet.
+  int export_buckets(const float* bounds, uint32_t B, double* dst, void* stream);
   // Node-wide statistics over the union of every rank's window (collective: every rank
   // of `comm` calls it with the same series layout): the same passes as refresh(), with
   // the ranks' pass-0 predictions and partials all-gathered and every digit histogram

@@ -33,6 +33,7 @@ SOURCES = [
     "long_window_brackets.hip",
     "node_window.hip",
     "window_buckets.hip",
+    "long_window_buckets.hip",
     "window_trend.hip",
     "calib.hip",
     "publish.hip",

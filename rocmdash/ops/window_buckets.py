@@ -2,7 +2,9 @@
 
 Kernel: ``csrc/window_buckets.hip`` (one wave64 per series: lane ``b`` counts the window
 samples <= bound ``b`` with one ``upper_bound`` in the series' sorted window, lane ``B``
-writes the valid count). Per series the result is ``B + 1`` counts: the valid (non-NaN)
+writes the valid count); for windows of more than 32768 samples, which keep no sorted
+state, ``csrc/long_window_buckets.hip`` (one stream of the time-major ring into per-series
+histograms, float64 counts). Per series the result is ``B + 1`` counts: the valid (non-NaN)
 samples ``x <= bounds[b]`` (fp32 compare: ties count, ``-0.0 == +0.0``, a ``-inf`` sample
 is in every bucket, a ``+inf`` sample only in the last), then the valid count, Prometheus'
 ``+Inf`` bucket. Unlike a percentile, buckets add up: across GPUs, nodes and scrapes,
@@ -22,6 +24,8 @@ from ..models.schema import METRIC_SPECS
 from .window_stats import MAX_WINDOW
 
 MAX_BUCKETS = 63  # finite bounds per series (csrc/window_buckets.h kMaxBuckets)
+MAX_LONG_WINDOW = 1 << 26  # the longest window rocmdash keeps (LongWindowSet)
+MAX_RING_STRIDE = 64  # floats per ring row (csrc/long_window_buckets.h kMaxBucketStride)
 POWER = "amd_gpu_average_package_power"
 VRAM = ("amd_gpu_used_vram", "amd_gpu_total_vram")
 DEFAULT_TOTAL_VRAM_MB = 288 * 1024  # an MI355X's HBM, when the GPU's own figure is unknown
@@ -63,12 +67,65 @@ def window_buckets_reference(x, bounds) -> np.ndarray:
     return out
 
 
+def bucket_ring_reference(rows, head: int, n: int, bounds) -> np.ndarray:
+    """Exact reference of ``bucket_ring``. ``rows``: host ``[depth, stride]``, a time-major
+    ring with row r at slot ``r & (depth - 1)`` (depth a power of two), whose window is rows
+    ``[head - n, head)``; ``bounds``: ``[cols, B]`` for the ring's first ``cols`` columns
+    (or ``[B]``: every column). Returns int64 ``[cols, B + 1]``."""
+    rows = np.asarray(rows, dtype=np.float32)
+    if rows.ndim != 2:
+        raise ValueError("rows must be [depth, stride]")
+    depth, stride = rows.shape
+    head, n = int(head), int(n)
+    if depth < 1 or depth & (depth - 1):
+        raise ValueError(f"the ring depth must be a power of two, got {depth}")
+    if not 0 <= n <= min(depth, head):
+        raise ValueError(f"a window of {n} rows does not fit a ring of {depth} rows at head {head}")
+    b = np.asarray(bounds, dtype=np.float32)
+    cols = stride if b.ndim == 1 else b.shape[0]
+    if not 1 <= cols <= stride:
+        raise ValueError(f"bounds are for {cols} series, the ring has {stride} columns")
+    slots = (np.arange(head - n, head, dtype=np.int64) & (depth - 1)) if n else np.zeros(0, np.int64)
+    return window_buckets_reference(rows[slots, :cols].T.reshape(cols, n), b)
+
+
+def long_window_buckets(x, bounds):
+    """``window_buckets`` for 32768 < n <= 2^26 samples per series (S <= 64), which no sorted
+    window holds: ``x`` [S, n] (device, float32, oldest first, NaN = invalid) is laid out
+    time-major as the first n rows of a ring of the next power-of-two depth and streamed
+    once by ``bucket_ring`` (csrc/long_window_buckets.hip) on the current stream. Returns
+    float64 [S, B + 1] on the device: a count may pass 2^24, where float32 stops being
+    exact. Shorter windows are accepted too (the same counts as ``window_buckets``)."""
+    import torch
+
+    from ..runtime.native import load
+
+    if not x.is_cuda:
+        raise ValueError("long_window_buckets runs on a GPU tensor; use window_buckets_reference on the CPU")
+    if x.ndim != 2:
+        raise ValueError("x must be [series, samples]")
+    S, n = x.shape
+    if n < 1 or n > MAX_LONG_WINDOW:
+        raise ValueError(f"window length must be in [1, {MAX_LONG_WINDOW}], got {n}")
+    if S > MAX_RING_STRIDE:
+        raise ValueError(f"at most {MAX_RING_STRIDE} series per call, got {S}")
+    b = np.array(check_bounds(bounds.detach().cpu().numpy() if isinstance(bounds, torch.Tensor) else bounds, S))
+    depth = 1 << (n - 1).bit_length()
+    ring = torch.full((depth, S), float("nan"), dtype=torch.float32, device=x.device)
+    ring[:n] = x.to(torch.float32).T
+    bd = torch.from_numpy(b).to(x.device)
+    out = torch.empty((S, b.shape[1] + 1), dtype=torch.float64, device=x.device)
+    load().bucket_ring(ring.data_ptr(), S, S, depth, n, n, bd.data_ptr(), b.shape[1], out.data_ptr(),
+                       torch.cuda.current_stream(x.device).cuda_stream)
+    return out
+
+
 def window_buckets(x, bounds):
     """Run the HIP kernel on a device tensor ``x`` [S, n] (float32, oldest first, NaN =
     invalid) with ``bounds`` [S, B] or [B]; returns float32 [S, B + 1] on the device
-    (exact counts: n <= 32768 < 2^24). The window is sorted with torch into one export
-    block ``[1, S, 1 + n]`` (count, ascending samples, +inf) and counted by
-    ``bucket_blocks`` on the current stream."""
+    (exact counts: n <= 32768 < 2^24; longer windows: ``long_window_buckets``). The window
+    is sorted with torch into one export block ``[1, S, 1 + n]`` (count, ascending samples,
+    +inf) and counted by ``bucket_blocks`` on the current stream."""
     import torch
 
     from ..runtime.native import load

@@ -46,6 +46,13 @@ CONTENT_TYPE = "text/plain; version=0.0.4; charset=utf-8"
 LAST = STAT_INDEX["last"]
 
 
+def node_bucket_sum(buckets: np.ndarray) -> np.ndarray:
+    """The node's le-buckets: per-GPU counts ``[N, S, B + 1]`` summed over the GPUs in
+    float64, in the dtype of the counts - float32 for short windows (N x 32768 < 2^24),
+    float64 for long ones, whose sums pass 2^24."""
+    return buckets.sum(axis=0, dtype=np.float64).astype(buckets.dtype)
+
+
 class SnapshotSource:
     """Produces (NodeSnapshot, self_metrics: Exposition) per scrape."""
 
@@ -86,7 +93,8 @@ class LocalNodeSource(SnapshotSource):
                  window_buckets: int | None = None, window_trend: int | None = None):
         """``window_buckets`` = B > 0 (default: ``ROCMDASH_WINDOW_BUCKETS``, else off): also
         export every series' window as B cumulative le-buckets + ``+Inf``
-        (``rocmdash_window_bucket``; GpuAgent.window_buckets) and their sum over the GPUs.
+        (``rocmdash_window_bucket``; GpuAgent.window_buckets) and their sum over the GPUs -
+        short windows as float32 counts, long windows (> 32768 samples) as float64.
         ``window_trend`` = P > 0 (default: ``ROCMDASH_WINDOW_TREND``, else off): the snapshot
         also carries every series' window as P + 1 columns of {min, max, mean, count}
         (GpuAgent.window_trend), served as JSON by ``GET /trend`` - never in ``/metrics``."""
@@ -171,7 +179,7 @@ class LocalNodeSource(SnapshotSource):
         if buckets is not None:
             snap.window_buckets = buckets
             snap.window_bucket_bounds = self.bucket_bounds
-            snap.node_window_buckets = buckets.sum(axis=0, dtype=np.float64).astype(np.float32)
+            snap.node_window_buckets = node_bucket_sum(buckets)
         if trend is not None:
             snap.window_trend, snap.window_trend_age_rows = trend, age
         exp = Exposition()
@@ -228,6 +236,11 @@ def render_trend(snap: NodeSnapshot) -> str | None:
 
 
 class Exporter:
+    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``). With window buckets on,
+    ``rocmdash_window_bucket`` / ``rocmdash_node_window_bucket`` carry exact integer counts
+    for any window the source keeps: up to 32768 samples from the resident sorted windows,
+    longer windows (up to 2^26) streamed from the device rings and printed from float64."""
+
     def __init__(self, source: SnapshotSource, hostname: str | None = None):
         self.source = source
         self.hostname = hostname or socket.gethostname()

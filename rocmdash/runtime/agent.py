@@ -538,12 +538,15 @@ class GpuAgent:
                               card_model=self.info.card_model)
 
     def window_buckets(self, bounds=None):
-        """Every series' window as cumulative le-buckets, ``[S, B + 1]`` float32: the valid
-        window samples <= each of ``bounds`` ([S, B] or [B], finite, strictly ascending;
-        default ``default_bucket_bounds()``), then the valid count (``+Inf``). On a GPU the
-        counts come from the resident sorted windows the last ``refresh()`` left on the
-        device (csrc/window_buckets.hip), in stream order, into a buffer the next call
-        reuses; the bounds are uploaded once per bounds object."""
+        """Every series' window as cumulative le-buckets, ``[S, B + 1]``: the valid window
+        samples <= each of ``bounds`` ([S, B] or [B], finite, strictly ascending; default
+        ``default_bucket_bounds()``), then the valid count (``+Inf``). On a GPU the counts
+        come from what the last ``refresh()`` left on the device, in stream order, into a
+        buffer the next call reuses; the bounds are uploaded once per bounds object. A
+        window of <= 32768 samples: float32, searched in the resident sorted windows
+        (csrc/window_buckets.hip). A long window (``cfg.long_window``): float64 - a count
+        may pass 2^24, where float32 stops being exact - streamed from the device rings
+        once per call (csrc/long_window_buckets.hip)."""
         import torch
 
         from ..ops.window_buckets import check_bounds, window_buckets_reference
@@ -554,14 +557,12 @@ class GpuAgent:
                 bounds = self._default_bounds = self.default_bucket_bounds()
         S = len(self.series)
         if self.dws is not None:
-            if not hasattr(self.dws, "export_buckets"):
-                raise ValueError("a window of > 32768 samples has no le-buckets: they are counted in the sorted "
-                                 "windows that only windows of <= 32768 samples keep resident (DeviceWindowSet)")
             cached = getattr(self, "_bucket_bounds", None)
             if cached is None or cached[0] is not bounds:
                 b = check_bounds(bounds, S)
                 dev = torch.from_numpy(b).to(self.device)
-                out = torch.empty((S, b.shape[1] + 1), dtype=torch.float32, device=self.device)
+                dtype = torch.float64 if self.cfg.long_window else torch.float32
+                out = torch.empty((S, b.shape[1] + 1), dtype=dtype, device=self.device)
                 cached = self._bucket_bounds = (bounds, dev, out)
             _, dev, out = cached
             self.dws.export_buckets(dev.data_ptr(), dev.shape[1], out.data_ptr(), _current_raw_stream(self.device_index))
@@ -571,7 +572,7 @@ class GpuAgent:
         for r in self.rings:
             rows, _ = r.window(self.window)
             blocks.append(rows.T if len(rows) else np.full((r.width, 1), np.nan, dtype=np.float32))
-        out, s = np.empty((S, b.shape[1] + 1), dtype=np.float32), 0
+        out, s = np.empty((S, b.shape[1] + 1), dtype=np.float64 if self.cfg.long_window else np.float32), 0
         for x in blocks:
             out[s : s + len(x)] = window_buckets_reference(x, b[s : s + len(x)])
             s += len(x)
