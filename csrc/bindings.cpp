@@ -15,6 +15,7 @@
 #include "rccl_comm.h"
 #include "long_window_buckets.h"
 #include "window_buckets.h"
+#include "window_excursions.h"
 #include "window_trend.h"
 
 namespace rocmdash {
@@ -379,6 +380,23 @@ PYBIND11_MODULE(_native, m) {
           "Enqueue every series' window trend after the last refresh: dst [S][columns + 1][4] floats "
           "(min, max, mean, count per slot of window / columns rows).")
       .def(
+          "export_excursions",
+          [](LongWindowSet& w, uintptr_t thresholds, uint32_t K, uintptr_t dst, uintptr_t work, size_t work_bytes,
+             uintptr_t stream) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_excursions(reinterpret_cast<const float*>(thresholds), K, reinterpret_cast<int32_t*>(dst),
+                                      reinterpret_cast<void*>(work), work_bytes, reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_excursions failed: " + std::to_string(e));
+          },
+          py::arg("thresholds_ptr"), py::arg("num_thresholds"), py::arg("dst_ptr"), py::arg("work_ptr"),
+          py::arg("work_bytes"), py::arg("stream"),
+          "Enqueue every series' window excursions after the last refresh: thresholds [S][K] floats -> dst [S][K][8] "
+          "int32 (above, valid, episodes, longest, current, since, leading, rows); work: a caller-owned workspace of "
+          "excursion_workspace_bytes(S, K) bytes.")
+      .def(
           "export_buckets",
           [](LongWindowSet& w, uintptr_t bounds, uint32_t B, uintptr_t dst, uintptr_t stream) {
             int e;
@@ -518,6 +536,23 @@ PYBIND11_MODULE(_native, m) {
           py::arg("columns"), py::arg("dst_ptr"), py::arg("stream"),
           "Enqueue every series' window trend after the last refresh: dst [S][columns + 1][4] floats "
           "(min, max, mean, count per slot of window / columns rows).")
+      .def(
+          "export_excursions",
+          [](const DeviceWindowSet& w, uintptr_t thresholds, uint32_t K, uintptr_t dst, uintptr_t work, size_t work_bytes,
+             uintptr_t stream) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_excursions(reinterpret_cast<const float*>(thresholds), K, reinterpret_cast<int32_t*>(dst),
+                                      reinterpret_cast<void*>(work), work_bytes, reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_excursions failed: " + std::to_string(e));
+          },
+          py::arg("thresholds_ptr"), py::arg("num_thresholds"), py::arg("dst_ptr"), py::arg("work_ptr"),
+          py::arg("work_bytes"), py::arg("stream"),
+          "Enqueue every series' window excursions after the last refresh: thresholds [S][K] floats -> dst [S][K][8] "
+          "int32 (above, valid, episodes, longest, current, since, leading, rows); work: a caller-owned workspace of "
+          "excursion_workspace_bytes(S, K) bytes.")
       .def("stats", [](const DeviceWindowSet& w) {
         auto st = w.stats();
         py::dict d;
@@ -763,6 +798,34 @@ PYBIND11_MODULE(_native, m) {
       py::arg("bounds_ptr"), py::arg("num_bounds"), py::arg("dst_ptr"), py::arg("stream"),
       "Cumulative le-buckets of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) whose window is "
       "rows [head - n, head): bounds [cols][B] floats -> dst [cols][B + 1] doubles.");
+  m.attr("MAX_EXCURSION_THRESHOLDS") = int(kMaxExcursionThresholds);
+  m.attr("MAX_EXCURSION_CHUNKS") = int(kMaxExcursionChunks);
+  m.def("excursion_workspace_bytes", &excursion_workspace_bytes, py::arg("series"), py::arg("num_thresholds"),
+        "Bytes of the caller-owned workspace of the excursion exports for `series` series (a ring's stride, or every "
+        "series of a set) and K thresholds; 0 for a K outside [1, 4].");
+  m.def("excursion_plan_chunk_rows", &excursion_plan_chunk_rows, py::arg("n"),
+        "Rows per chunk the excursion stream plans for a window of n rows.");
+  m.def("excursion_chunk_count", &excursion_chunk_count, py::arg("depth"), py::arg("head"), py::arg("n"),
+        py::arg("chunk_rows"), "Chunks of the window [head - n, head) of a ring of depth rows cut every chunk_rows rows.");
+  m.def(
+      "excursion_ring",
+      [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n, uintptr_t thresholds,
+         uint32_t K, uint32_t chunk_rows, uintptr_t dst, uintptr_t work, size_t work_bytes, uintptr_t stream) {
+        int e;
+        {
+          py::gil_scoped_release nogil;
+          e = launch_excursion_ring(reinterpret_cast<const float*>(base), stride, cols, depth, head, n,
+                                    reinterpret_cast<const float*>(thresholds), K, chunk_rows,
+                                    reinterpret_cast<int32_t*>(dst), reinterpret_cast<void*>(work), work_bytes,
+                                    reinterpret_cast<void*>(stream));
+        }
+        if (e != 0) throw std::runtime_error("excursion_ring failed: " + std::to_string(e));
+      },
+      py::arg("base_ptr"), py::arg("stride"), py::arg("cols"), py::arg("depth"), py::arg("head"), py::arg("n"),
+      py::arg("thresholds_ptr"), py::arg("num_thresholds"), py::arg("chunk_rows"), py::arg("dst_ptr"), py::arg("work_ptr"),
+      py::arg("work_bytes"), py::arg("stream"),
+      "Window excursions of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) whose window is rows "
+      "[head - n, head): thresholds [cols][K] floats -> dst [cols][K][8] int32. chunk_rows 0 plans the chunks.");
   m.attr("MAX_TREND_COLUMNS") = int(kMaxTrendColumns);
   m.attr("MAX_TREND_ROWS_PER_COLUMN") = int(kMaxTrendRowsPerColumn);
   m.def(

@@ -96,6 +96,14 @@ class DeviceWindowSet {
   // after invalidate()). P a power of two in [8, 1024], <= window. Returns a hipError_t
   // (hipErrorInvalidValue before any launch for a bad argument).
   int export_trend(uint32_t P, float* dst, void* stream) const;
+  // Enqueue, after the refresh that produced it, every series' window excursions
+  // (window_excursions.h, defined in window_excursions.hip) over the window of the last
+  // refresh: thresholds device [num_series][K], dst device [num_series][K][8] int32 (all
+  // zeroes before the first refresh and after invalidate()), work the caller's workspace of
+  // at least excursion_workspace_bytes(num_series, K) bytes. Returns a hipError_t
+  // (hipErrorInvalidValue before any launch or write for a bad argument).
+  int export_excursions(const float* thresholds, uint32_t K, int32_t* dst, void* work, size_t work_bytes,
+                        void* stream) const;
   WindowSetStats stats() const { return st_; }
   // Tagged waits that found part of their refresh overwritten by a newer one (they
   // returned false and copied nothing usable: never a mix of two refreshes).

@@ -258,6 +258,14 @@ class LongWindowSet {
   // hipError_t as export_trend does: hipErrorInvalidValue before any launch or write for a
   // bad argument, hipErrorNotReady while rows are staged that no kernel has written yet.
   int export_buckets(const float* bounds, uint32_t B, double* dst, void* stream);
+  // Enqueue, after the refresh that left it on the device, every series' window excursions
+  // (window_excursions.h, defined in window_excursions.hip): thresholds device
+  // [num_series][K], dst device [num_series][K][8] int32, work the caller's workspace of at
+  // least excursion_workspace_bytes(num_series, K) bytes. Rows the host ring lost count as
+  // invalid. Returns a hipError_t as export_trend does: hipErrorInvalidValue before any
+  // launch or write for a bad argument, hipErrorNotReady while rows are staged that no
+  // kernel has written yet.
+  int export_excursions(const float* thresholds, uint32_t K, int32_t* dst, void* work, size_t work_bytes, void* stream);
   // Node-wide statistics over the union of every rank's window (collective: every rank
   // of `comm` calls it with the same series layout): the same passes as refresh(), with
   // the ranks' pass-0 predictions and partials all-gathered and every digit histogram

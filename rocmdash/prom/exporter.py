@@ -90,15 +90,28 @@ class LocalNodeSource(SnapshotSource):
     """Every visible GPU in this process, background sampling, stats per scrape."""
 
     def __init__(self, devices=None, source: str = "auto", counters: str = "auto", cfg=None,
-                 window_buckets: int | None = None, window_trend: int | None = None):
+                 window_buckets: int | None = None, window_trend: int | None = None, window_excursions=None,
+                 replay=None):
         """``window_buckets`` = B > 0 (default: ``ROCMDASH_WINDOW_BUCKETS``, else off): also
         export every series' window as B cumulative le-buckets + ``+Inf``
         (``rocmdash_window_bucket``; GpuAgent.window_buckets) and their sum over the GPUs -
         short windows as float32 counts, long windows (> 32768 samples) as float64.
         ``window_trend`` = P > 0 (default: ``ROCMDASH_WINDOW_TREND``, else off): the snapshot
         also carries every series' window as P + 1 columns of {min, max, mean, count}
-        (GpuAgent.window_trend), served as JSON by ``GET /trend`` - never in ``/metrics``."""
+        (GpuAgent.window_trend), served as JSON by ``GET /trend`` - never in ``/metrics``.
+        ``window_excursions`` = ``"F1,F2,.."`` or a sequence of 1 to 4 increasing fractions in
+        (0, 1] (default: ``ROCMDASH_WINDOW_EXCURSIONS``, else off): also export every series'
+        episodes above those fractions of its axis (``rocmdash_window_excursions`` and its
+        neighbours; GpuAgent.window_excursions). ``replay``: the recording of ``source="replay"``."""
         from ..runtime import native
+
+        if window_excursions is None:
+            window_excursions = os.environ.get("ROCMDASH_WINDOW_EXCURSIONS", "") or None
+        self.excursion_fractions = None
+        if window_excursions is not None:  # checked before any agent starts its samplers
+            from ..ops.window_excursions import parse_fractions
+
+            self.excursion_fractions = parse_fractions(window_excursions)
 
         if window_trend is None:
             window_trend = int(os.environ.get("ROCMDASH_WINDOW_TREND", "0") or 0)
@@ -119,7 +132,8 @@ class LocalNodeSource(SnapshotSource):
         devices = list(range(n)) if devices is None else list(devices)
         if not devices:
             raise RuntimeError("no GPU visible to the exporter (use --synthetic N for a synthetic node)")
-        self.agents = [GpuAgent(d, source=source, counters=counters, cfg=cfg) for d in devices]
+        kw = {"replay": replay} if replay is not None else {}
+        self.agents = [GpuAgent(d, source=source, counters=counters, cfg=cfg, **kw) for d in devices]
         series = {a.series for a in self.agents}
         if len(series) != 1:
             raise RuntimeError(f"GPUs disagree on the series layout: {series}")
@@ -134,6 +148,9 @@ class LocalNodeSource(SnapshotSource):
             window_buckets = int(os.environ.get("ROCMDASH_WINDOW_BUCKETS", "0") or 0)
         # one set of bounds for the node (the first GPU's caps): buckets add up only over the same bounds
         self.bucket_bounds = self.agents[0].default_bucket_bounds(int(window_buckets)) if window_buckets else None
+        # likewise one set of thresholds for the node
+        self.excursion_thresholds = (self.agents[0].default_excursion_thresholds(self.excursion_fractions)
+                                     if self.excursion_fractions else None)
 
     def collect(self):
         import torch
@@ -148,11 +165,16 @@ class LocalNodeSource(SnapshotSource):
             if self.trend_columns is not None:  # likewise: the rings as this refresh left them
                 trend = [a.window_trend(self.trend_columns) for a in self.agents]
                 age = self.agents[0].trend_age_rows(self.trend_columns)
+            excursions = None
+            if self.excursion_thresholds is not None:
+                excursions = [a.window_excursions(self.excursion_thresholds) for a in self.agents]
             host = np.stack([o.to("cpu", non_blocking=False).numpy() for o in outs])
             if buckets is not None:
                 buckets = np.stack([b.to("cpu", non_blocking=False).numpy() for b in buckets])
             if trend is not None:
                 trend = np.stack([t.to("cpu", non_blocking=False).numpy() for t in trend])
+            if excursions is not None:
+                excursions = np.stack([e.to("cpu", non_blocking=False).numpy() for e in excursions])
             now_ns = time.time_ns()
             for i, a in enumerate(self.agents):
                 a.health_rows(self._health[i], now_ns)
@@ -182,6 +204,8 @@ class LocalNodeSource(SnapshotSource):
             snap.node_window_buckets = node_bucket_sum(buckets)
         if trend is not None:
             snap.window_trend, snap.window_trend_age_rows = trend, age
+        if excursions is not None:
+            snap.window_excursions, snap.window_excursion_thresholds = excursions, self.excursion_thresholds
         exp = Exposition()
         for a, gid in zip(self.agents, ids):
             for sampler in a.samplers:
@@ -357,7 +381,8 @@ def main(argv=None) -> int:
     ap.add_argument("--host", default="0.0.0.0")
     ap.add_argument("--port", type=int, default=config.EXPORTER_PORT)
     ap.add_argument("--synthetic", type=int, default=0, help="serve a synthetic node with N GPUs")
-    ap.add_argument("--source", default="auto", choices=["auto", "hw", "synthetic"])
+    ap.add_argument("--source", default="auto", choices=["auto", "hw", "synthetic", "replay"])
+    ap.add_argument("--replay", default=None, metavar="NPZ", help="the recording --source replay plays")
     ap.add_argument("--counters", default="auto", choices=["auto", "hw", "synthetic", "off"])
     ap.add_argument("--window-buckets", type=int, default=None, metavar="B",
                     help="also export every series' window as B cumulative le-buckets (1..63; default "
@@ -365,10 +390,21 @@ def main(argv=None) -> int:
     ap.add_argument("--window-trend", type=int, default=None, metavar="P",
                     help="also serve GET /trend: every series' window as P + 1 columns of min / max / mean / count "
                          "(a power of two in 8..1024; default ROCMDASH_WINDOW_TREND, else off)")
+    ap.add_argument("--window-excursions", default=None, metavar="F1,F2,..",
+                    help="also export every series' episodes above these fractions of its axis: 1 to 4 increasing "
+                         "fractions in (0, 1], e.g. 0.5,0.9 (default ROCMDASH_WINDOW_EXCURSIONS, else off)")
     args = ap.parse_args(argv)
+    if args.window_excursions is not None:
+        from ..ops.window_excursions import parse_fractions
+
+        try:
+            parse_fractions(args.window_excursions)
+        except ValueError as e:
+            ap.error(f"--window-excursions: {e}")
     logging.basicConfig(level=logging.INFO)
     src = SyntheticSource(args.synthetic) if args.synthetic else LocalNodeSource(
-        source=args.source, counters=args.counters, window_buckets=args.window_buckets, window_trend=args.window_trend)
+        source=args.source, counters=args.counters, window_buckets=args.window_buckets, window_trend=args.window_trend,
+        window_excursions=args.window_excursions, replay=args.replay)
     exp = Exporter(src)
     exp.serve(args.host, args.port)
     log.info("serving /metrics on %s:%d", args.host, exp.port)

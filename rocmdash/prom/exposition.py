@@ -138,6 +138,7 @@ def render_snapshot(snap, hostname: str = "", extra_labels: dict | None = None, 
                 exp.add("rocmdash_node_window", snap.node_window[si, STAT_NAMES.index(sname)], lab,
                         "Window statistic of a series over every GPU's window at once (node-wide)")
     render_window_buckets(exp, snap, hostname, extra)
+    render_window_excursions(exp, snap, hostname, extra)
     return exp.text()
 
 
@@ -175,6 +176,38 @@ def render_window_buckets(exp: Exposition, snap, hostname: str = "", extra: dict
             for b, lab_le in enumerate(le[si]):
                 exp.add("rocmdash_node_window_bucket", node[si, b], dict(base, metric=series, le=lab_le),
                         BUCKET_HELP + " (every GPU's window of the node at once)")
+
+
+# family -> (field of a record, HELP); rocmdash.ops.window_excursions states the semantics
+EXCURSION_FAMILIES = (
+    ("rocmdash_window_excursions", 2, "Episodes (maximal runs of valid samples above the threshold) in a series' last W samples"),
+    ("rocmdash_window_excursion_longest_samples", 3, "Length of the longest episode above the threshold, in valid samples"),
+    ("rocmdash_window_excursion_current_samples", 4,
+     "Length of the episode the newest valid sample is in, in valid samples (0: not above now)"),
+    ("rocmdash_window_excursion_since_samples", 5,
+     "Valid samples since the last episode ended (0 while above; the window's valid samples if there was none)"),
+    ("rocmdash_window_above_samples", 0, "Valid samples above the threshold in a series' last W samples"),
+)
+
+
+def render_window_excursions(exp: Exposition, snap, hostname: str = "", extra: dict | None = None) -> None:
+    """The five excursion gauge families, labelled ``{gpu_id, metric, threshold}``, when the
+    snapshot carries them (``NodeSnapshot.window_excursions`` [N, S, K, 8] and
+    ``window_excursion_thresholds`` [S, K]). Values are integers; the threshold label is
+    printed as the buckets' ``le``."""
+    exc = getattr(snap, "window_excursions", None)
+    thr = getattr(snap, "window_excursion_thresholds", None)
+    if exc is None or thr is None or not len(snap.window_series):
+        return
+    for name, field, help_ in EXCURSION_FAMILIES:
+        for g, gid in enumerate(snap.gpu_ids):
+            base = {"gpu_id": gid, "card_model": snap.card_models[g] or ""}
+            if hostname:
+                base["hostname"] = hostname
+            base.update(extra or {})
+            for si, series in enumerate(snap.window_series):
+                for k in range(len(thr[si])):
+                    exp.add(name, int(exc[g, si, k, field]), dict(base, metric=series, threshold=repr(float(thr[si][k]))), help_)
 
 
 def render_health(exp: Exposition, health, gpu_ids, hostname: str = "", extra: dict | None = None) -> None:

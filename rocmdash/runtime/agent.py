@@ -618,6 +618,57 @@ class GpuAgent:
         h = int(self.rings[ring_index].head)
         return trend_age_rows(h, min(h, self.window), self.window, int(columns))
 
+    def default_excursion_thresholds(self, fractions=(0.5, 0.75, 0.9)) -> np.ndarray:
+        """``[S, K]`` float32 thresholds of this GPU's series: ``fractions`` of each series'
+        axis, the axis of ``default_bucket_bounds``
+        (``rocmdash.ops.window_excursions.default_thresholds``)."""
+        from ..ops.window_excursions import default_thresholds
+
+        vram = self.smi_source.info().get("vram_total_mb")
+        return default_thresholds(self.series, self.info.power_limit_w, float(vram) if vram else None, fractions,
+                                  card_model=self.info.card_model)
+
+    def window_excursions(self, thresholds=None):
+        """Every series' episodes above its thresholds, ``[S, K, 8]`` int32: ``{above, valid,
+        episodes, longest, current, since, leading, rows}`` per threshold
+        (``rocmdash.ops.window_excursions`` states the semantics; ``thresholds`` [S, K] or
+        [K], default ``default_excursion_thresholds()``). On a GPU the records are reduced in
+        time order from the device rings the last ``refresh()`` left there
+        (csrc/window_excursions.hip), short or long windows alike, in stream order; the
+        thresholds are uploaded once per thresholds object and the output and the workspace
+        are reused by the next call."""
+        import torch
+
+        from ..ops.window_excursions import check_thresholds, window_excursions_reference
+
+        if thresholds is None:
+            thresholds = getattr(self, "_default_thresholds", None)
+            if thresholds is None:
+                thresholds = self._default_thresholds = self.default_excursion_thresholds()
+        S = len(self.series)
+        if self.dws is not None:
+            cached = getattr(self, "_excursions", None)
+            if cached is None or cached[0] is not thresholds:
+                from .native import load
+
+                t = check_thresholds(thresholds, S)
+                dev = torch.from_numpy(t).to(self.device)
+                out = torch.empty((S, t.shape[1], 8), dtype=torch.int32, device=self.device)
+                work = torch.empty(load().excursion_workspace_bytes(S, t.shape[1]), dtype=torch.uint8, device=self.device)
+                cached = self._excursions = (thresholds, dev, out, work)
+            _, dev, out, work = cached
+            self.dws.export_excursions(dev.data_ptr(), dev.shape[1], out.data_ptr(), work.data_ptr(), work.numel(),
+                                       _current_raw_stream(self.device_index))
+            return out
+        t = check_thresholds(thresholds, S)
+        out, s = np.empty((S, t.shape[1], 8), dtype=np.int32), 0
+        for r in self.rings:
+            rows, _ = r.window(self.window)
+            rows = np.asarray(rows, dtype=np.float32).reshape(-1, r.width)
+            out[s : s + r.width] = window_excursions_reference(rows, t[s : s + r.width])
+            s += r.width
+        return torch.from_numpy(out)
+
     def window_host(self, ring_index: int = 0):
         """Newest window of a ring on the host (oldest first) - for tests/debug."""
         return self.rings[ring_index].window(self.window)

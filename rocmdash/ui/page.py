@@ -179,6 +179,29 @@ def window_trend_figures(snap: NodeSnapshot, selected=None, height: int = 220) -
     return figs
 
 
+def window_excursion_tables(snap: NodeSnapshot, selected=None) -> dict | None:
+    """{"GPU <id>": [{metric, threshold, episodes, longest, current, since}, ...]}: per selected
+    GPU one table of the window excursions (``rocmdash.ops.window_excursions``; lengths in
+    valid samples), one row per series and threshold (None if the snapshot carries none)."""
+    exc = getattr(snap, "window_excursions", None)
+    thr = getattr(snap, "window_excursion_thresholds", None)
+    if exc is None or thr is None:
+        return None
+    from ..ops.window_excursions import E_CURRENT, E_EPISODES, E_LONGEST, E_SINCE
+
+    sel = set(str(g) for g in selected) if selected is not None else None
+    tables = {}
+    for g, gid in enumerate(snap.gpu_ids):
+        if sel is not None and gid not in sel:
+            continue
+        tables[f"GPU {gid}"] = [
+            {"metric": series, "threshold": float(thr[si][k]), "episodes": int(exc[g, si, k, E_EPISODES]),
+             "longest": int(exc[g, si, k, E_LONGEST]), "current": int(exc[g, si, k, E_CURRENT]),
+             "since": int(exc[g, si, k, E_SINCE])}
+            for si, series in enumerate(snap.window_series) for k in range(len(thr[si]))]
+    return tables or None
+
+
 def xcd_table(snap: NodeSnapshot, selected=None) -> dict | None:
     """{"GPU <id>": {"XCD <x> busy %": v, "XCD <x> MHz": v, ...}} of the selected GPUs'
     per-XCD detail (None if the data source has none)."""
@@ -202,7 +225,7 @@ def xcd_table(snap: NodeSnapshot, selected=None) -> dict | None:
 
 
 def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xcd: dict | None = None,
-                  buckets: dict | None = None, trend: list | None = None) -> None:
+                  buckets: dict | None = None, trend: list | None = None, excursions: dict | None = None) -> None:
     st.subheader("Average Metrics (Selected GPUs)")
     avg_cols = st.columns(4)
     for col, (key, spec) in zip(avg_cols, frame.avg_panels):
@@ -239,6 +262,11 @@ def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xc
             for col, (key, fig) in zip(st.columns(4), trend[i : i + 4]):
                 with col:
                     st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
+    if extended and excursions:
+        st.subheader("Window Excursions (episodes above a threshold; lengths in valid samples)")
+        for title, rows in excursions.items():
+            st.markdown(f"**{title}**")
+            st.dataframe(pd.DataFrame(rows), use_container_width=True)
     if extended and xcd is not None:
         st.subheader("Per-XCD Activity and Clocks")
         st.dataframe(pd.DataFrame.from_dict(xcd, orient="index"), use_container_width=True)
@@ -309,7 +337,8 @@ def main(max_refreshes: int | None = None, data_source: str | None = None) -> No
                 _render_frame(st, frame, extended, node_window_table(snap) if extended else None,
                               xcd_table(snap, st.session_state.selected_gpus) if extended else None,
                               window_bucket_table(snap) if extended else None,
-                              window_trend_figures(snap, st.session_state.selected_gpus) if extended else None)
+                              window_trend_figures(snap, st.session_state.selected_gpus) if extended else None,
+                              window_excursion_tables(snap, st.session_state.selected_gpus) if extended else None)
         n += 1
         if max_refreshes is not None and n >= max_refreshes:
             break

@@ -112,6 +112,11 @@ class NodeSnapshot:
     # the first ring's rows (another ring's newest column differs by less than one column)
     window_trend: np.ndarray | None = None
     window_trend_age_rows: np.ndarray | None = None
+    # Window excursions (rocmdash.ops.window_excursions), when computed: per GPU
+    # [N, S, K, 8] int32 - {above, valid, episodes, longest, current, since, leading, rows}
+    # per threshold of window_excursion_thresholds [S, K]
+    window_excursions: np.ndarray | None = None
+    window_excursion_thresholds: np.ndarray | None = None
 
     def __post_init__(self):
         self.values = np.asarray(self.values, dtype=np.float64)
