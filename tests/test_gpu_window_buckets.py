@@ -10,34 +10,12 @@ import numpy as np
 import pytest
 
 import _exact
+from _bucket_bounds import bounds_row as _bounds_row
+from _bucket_bounds import one_shot_rows as _one_shot_rows
 
 pytestmark = pytest.mark.gpu
 
 KINDS = ("on_samples", "between")
-
-
-def _bounds_row(v, B, kind):
-    """B finite, strictly ascending fp32 bounds for one series from its valid samples ``v``:
-    ``on_samples`` = every k-th distinct sorted sample itself; ``between`` = one ulp above or
-    below such a sample (alternating): between its neighbours where they are a few ulp apart.
-    Series with fewer than B distinct finite samples get further bounds one ulp apart above
-    the last (or around 0 with no sample at all)."""
-    f32 = np.float32
-    c = np.unique(v[np.isfinite(v)]).astype(f32)  # ascending, -0.0 == +0.0 merged
-    if len(c):
-        c = c[np.unique(np.linspace(0, len(c) - 1, min(B, len(c))).astype(np.int64))]
-        if kind == "between":
-            toward = np.where(np.arange(len(c)) % 2 == 0, f32(np.inf), f32(-np.inf)).astype(f32)
-            c = np.unique(np.nextafter(c, toward).astype(f32))
-            c = c[np.isfinite(c)]
-    out = [f32(x) for x in c]
-    if not out:
-        out = [f32(-1e-45)]
-    while len(out) < B:
-        out.append(np.nextafter(out[-1], f32(np.inf)).astype(f32))
-    out = np.array(out[:B], f32)
-    assert np.isfinite(out).all() and (np.diff(out) > 0).all()
-    return out
 
 
 def _bounds(x, B, kinds):
@@ -54,22 +32,6 @@ def _assert_counts(got, x, bounds, what=""):
     np.testing.assert_array_equal(got.astype(np.int64), want, err_msg=what)
     np.testing.assert_array_equal(got, want.astype(np.float32), err_msg=what)  # whole numbers, nothing else
     return want
-
-
-_ROWS = {}
-
-
-def _one_shot_rows(n):
-    """[S, n]: the 21 families, + a constant run, + one series with -inf and +inf at its ends."""
-    if n not in _ROWS:
-        rng = np.random.default_rng(n + 3)
-        x = _exact.family_rows(rng, 0, n, n, width=len(_exact.FAMILIES), blips=(n // 2,)).T
-        ends = rng.normal(0, 1, n).astype(np.float32)
-        ends[0], ends[-1] = -np.inf, np.inf  # n = 1: the one sample is +inf
-        x = np.concatenate([x, np.full((1, n), -7.25, np.float32), ends[None]])
-        x.setflags(write=False)
-        _ROWS[n] = x
-    return _ROWS[n]
 
 
 @pytest.mark.parametrize("kind", KINDS)

@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+import _bucket_bounds as bb
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = "/opt/rocm/bin/hipcc"
 
@@ -50,6 +52,73 @@ def test_bucket_ring_reference_against_brute_force(depth, stride, cols, head, n)
     if cols == stride:  # [B]: the same bounds for every column
         np.testing.assert_array_equal(bucket_ring_reference(rows, head, n, bounds[0]),
                                       _brute(rows, head, n, np.tile(bounds[0], (cols, 1))))
+
+
+@pytest.mark.parametrize("B", [1, 2, 3, 16, 63])
+@pytest.mark.parametrize("name", bb.BOUNDS)
+def test_bounds_families_are_bounds_and_the_reference_counts_them(name, B):
+    """Every family of tests/_bucket_bounds.py is finite and strictly ascending at every B
+    the GPU tests use, and ``bucket_ring_reference`` on it - every sample family in one ring,
+    a wrapped window - is the brute-force ``x <= b`` count."""
+    from rocmdash.ops.window_buckets import bucket_ring_reference, check_bounds
+
+    depth, head, n = 64, (1 << 32) + 37, 50
+    rng = np.random.default_rng(B + len(name))
+    cols = [bb.column(rng, name, kind, 2 + j, depth, B) for j, kind in enumerate(bb.SAMPLE_KINDS)]
+    bounds = np.stack([b for b, _ in cols])
+    assert bounds.dtype == np.float32 and bounds.shape == (len(cols), B)
+    np.testing.assert_array_equal(check_bounds(bounds), bounds)
+    rows = np.stack([x for _, x in cols] + [np.full(depth, 1.0, np.float32)], axis=1)  # + an unread column
+    assert rows.dtype == np.float32
+    got = bucket_ring_reference(rows, head, n, bounds)
+    np.testing.assert_array_equal(got, _brute(rows, head, n, bounds))
+    assert got[:, -1].max() == n
+
+
+def _even_bounds(cols, B):
+    """``_bounds`` of tests/test_gpu_long_window_buckets.py: what every streaming test used."""
+    step = (0.5 + 0.25 * np.arange(cols, dtype=np.float32))[:, None]
+    return np.ascontiguousarray((np.arange(B, dtype=np.float32) - np.float32(B // 2))[None, :] * step)
+
+
+@pytest.mark.parametrize("B", [16, 63])
+def test_uneven_bounds_need_the_walk_and_even_ones_do_not(B):
+    """The fp32 model of the kernel's guess on ``hop`` samples: the uneven families are far
+    off it - geometric bounds at least B / 4 bins below the sample's bin (the walk goes up),
+    their mirror image as far above (down), a span that overflows B - 1 bins up from bin 0,
+    denormal and clustered bounds B / 4 bins one way or the other - while on the evenly
+    spaced bounds of tests/test_gpu_long_window_buckets.py no sample of any family is more
+    than ONE bin from its guess: those tests never drove the walk."""
+    rng = np.random.default_rng(B)
+    reached = {}
+    for name in bb.WALKS:
+        b = bb.bounds_for(name, B)
+        x = bb.hop(rng, 1024, b)
+        assert (np.diff(np.searchsorted(b, x, "left")) != 0).all(), f"{name}: a hop sample stayed in its bin"
+        reached[name] = bb.walk_reached(x, b)
+        assert bb.walks_enough(name, x, b), (name, reached[name])
+    print(f"[walk] B = {B}: (up, down) {reached}")
+    assert reached["geometric"][0] >= B // 4 and reached["geometric_down"][1] >= B // 4
+    assert reached["huge_span"][0] >= B - 1
+    assert max(reached["denormal"]) >= B // 4 and max(reached["clustered"]) >= B // 4
+    even = _even_bounds(8, B)
+    for c in range(8):
+        for kind in bb.SAMPLE_KINDS:
+            x = bb.exact_column(rng, c, 4096) if kind == "exact" else bb.SAMPLES[kind](rng, 4096, even[c])
+            assert max(bb.walk_reached(x, even[c])) <= 1, (c, kind)
+        wide = (rng.normal(0, 1, 4096) * float(even[c, -1])).astype(np.float32)  # the ROLES' normal samples
+        assert max(bb.walk_reached(wide, even[c])) <= 1, c
+
+
+def test_guess_distance_is_the_kernels_clamp():
+    """NaN -> 0 (inf x 0, 0 x inf), -inf -> 0, +inf -> B; a NaN sample takes no walk."""
+    b = bb.huge_span(16)
+    x = np.array([-np.inf, np.inf, np.nan, b[0], b[-1]], np.float32)
+    np.testing.assert_array_equal(bb.guess_distance(x, b), [0, 16, 0, 0, 15])  # every guess is bin 0
+    b = bb.denormal(16)  # bins per unit is inf: b[0] -> 0 x inf = NaN -> 0, all above it -> B
+    x = np.array([-np.inf, np.inf, b[0], b[1], b[-1], 1.0], np.float32)
+    np.testing.assert_array_equal(bb.guess_distance(x, b), [0, 0, 0, 1 - 16, 15 - 16, 0])
+    np.testing.assert_array_equal(bb.guess_distance(np.array([0.5], np.float32), np.array([1.0], np.float32)), [0])
 
 
 def test_bucket_ring_reference_rejects_bad_rings():
