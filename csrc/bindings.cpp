@@ -16,6 +16,7 @@
 #include "long_window_buckets.h"
 #include "window_buckets.h"
 #include "window_excursions.h"
+#include "window_heatmap.h"
 #include "window_trend.h"
 
 namespace rocmdash {
@@ -380,6 +381,20 @@ PYBIND11_MODULE(_native, m) {
           "Enqueue every series' window trend after the last refresh: dst [S][columns + 1][4] floats "
           "(min, max, mean, count per slot of window / columns rows).")
       .def(
+          "export_heatmap",
+          [](LongWindowSet& w, uint32_t P, uintptr_t bounds, uint32_t B, uintptr_t dst, uintptr_t stream) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_heatmap(P, reinterpret_cast<const float*>(bounds), B, reinterpret_cast<int32_t*>(dst),
+                                   reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_heatmap failed: " + std::to_string(e));
+          },
+          py::arg("columns"), py::arg("bounds_ptr"), py::arg("num_bounds"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue every series' window heatmap after the last refresh: bounds [S][B] floats -> dst "
+          "[S][columns + 1][B + 1] int32 (per-bin counts per slot of window / columns rows).")
+      .def(
           "export_excursions",
           [](LongWindowSet& w, uintptr_t thresholds, uint32_t K, uintptr_t dst, uintptr_t work, size_t work_bytes,
              uintptr_t stream) {
@@ -536,6 +551,20 @@ PYBIND11_MODULE(_native, m) {
           py::arg("columns"), py::arg("dst_ptr"), py::arg("stream"),
           "Enqueue every series' window trend after the last refresh: dst [S][columns + 1][4] floats "
           "(min, max, mean, count per slot of window / columns rows).")
+      .def(
+          "export_heatmap",
+          [](const DeviceWindowSet& w, uint32_t P, uintptr_t bounds, uint32_t B, uintptr_t dst, uintptr_t stream) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_heatmap(P, reinterpret_cast<const float*>(bounds), B, reinterpret_cast<int32_t*>(dst),
+                                   reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_heatmap failed: " + std::to_string(e));
+          },
+          py::arg("columns"), py::arg("bounds_ptr"), py::arg("num_bounds"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue every series' window heatmap after the last refresh: bounds [S][B] floats -> dst "
+          "[S][columns + 1][B + 1] int32 (per-bin counts per slot of window / columns rows).")
       .def(
           "export_excursions",
           [](const DeviceWindowSet& w, uintptr_t thresholds, uint32_t K, uintptr_t dst, uintptr_t work, size_t work_bytes,
@@ -844,6 +873,24 @@ PYBIND11_MODULE(_native, m) {
       py::arg("columns"), py::arg("rows_per_col"), py::arg("dst_ptr"), py::arg("stream"),
       "Window trend of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) whose window is rows "
       "[head - n, head): dst [cols][columns + 1][4] floats (min, max, mean, count per slot of rows_per_col rows).");
+  m.def(
+      "heatmap_ring",
+      [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n, uint32_t P,
+         uint32_t rows_per_col, uintptr_t bounds, uint32_t B, uintptr_t dst, uintptr_t stream) {
+        int e;
+        {
+          py::gil_scoped_release nogil;
+          e = launch_heatmap_ring(reinterpret_cast<const float*>(base), stride, cols, depth, head, n, P, rows_per_col,
+                                  reinterpret_cast<const float*>(bounds), B, reinterpret_cast<int32_t*>(dst),
+                                  reinterpret_cast<void*>(stream));
+        }
+        if (e != 0) throw std::runtime_error("heatmap_ring failed: " + std::to_string(e));
+      },
+      py::arg("base_ptr"), py::arg("stride"), py::arg("cols"), py::arg("depth"), py::arg("head"), py::arg("n"),
+      py::arg("columns"), py::arg("rows_per_col"), py::arg("bounds_ptr"), py::arg("num_bounds"), py::arg("dst_ptr"),
+      py::arg("stream"),
+      "Window heatmap of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) whose window is rows "
+      "[head - n, head): bounds [cols][B] floats -> dst [cols][columns + 1][B + 1] int32 (per-bin counts per slot).");
 
   // ---- native frame renderer (csrc/frame_render.h) ---------------------------------
   py::class_<FramePlan, std::shared_ptr<FramePlan>>(m, "FramePlan")

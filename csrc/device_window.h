@@ -96,6 +96,13 @@ class DeviceWindowSet {
   // after invalidate()). P a power of two in [8, 1024], <= window. Returns a hipError_t
   // (hipErrorInvalidValue before any launch for a bad argument).
   int export_trend(uint32_t P, float* dst, void* stream) const;
+  // Enqueue, after the refresh that produced it, every series' window heatmap
+  // (window_heatmap.h, defined in window_heatmap.hip): the slots of export_trend, each
+  // binned by bounds device [num_series][B] (as export_buckets); dst device
+  // [num_series][P + 1][B + 1] int32 per-bin counts, every one written (all zeroes before the
+  // first refresh and after invalidate()). Returns a hipError_t (hipErrorInvalidValue before
+  // any launch or write for a bad argument).
+  int export_heatmap(uint32_t P, const float* bounds, uint32_t B, int32_t* dst, void* stream) const;
   // Enqueue, after the refresh that produced it, every series' window excursions
   // (window_excursions.h, defined in window_excursions.hip) over the window of the last
   // refresh: thresholds device [num_series][K], dst device [num_series][K][8] int32 (all

@@ -251,6 +251,12 @@ class LongWindowSet {
   // are staged that no kernel has written yet (between stage() and its flush: never after
   // refresh()).
   int export_trend(uint32_t P, float* dst, void* stream);
+  // Enqueue, after the refresh that left it on the device, every series' window heatmap
+  // (window_heatmap.h, defined in window_heatmap.hip): the slots of export_trend, each
+  // binned by bounds device [num_series][B]; dst device [num_series][P + 1][B + 1] int32
+  // per-bin counts, every one written. Rows the host ring lost count as invalid. Returns a
+  // hipError_t as export_trend does.
+  int export_heatmap(uint32_t P, const float* bounds, uint32_t B, int32_t* dst, void* stream);
   // Enqueue, after the refresh that left it on the device, every series' cumulative
   // le-buckets (long_window_buckets.h, defined in long_window_buckets.hip): bounds device
   // [num_series][B], dst device [num_series][B + 1] doubles, series in set order. One

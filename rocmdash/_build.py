@@ -35,6 +35,7 @@ SOURCES = [
     "window_buckets.hip",
     "long_window_buckets.hip",
     "window_trend.hip",
+    "window_heatmap.hip",
     "window_excursions.hip",
     "calib.hip",
     "publish.hip",

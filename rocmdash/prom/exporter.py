@@ -91,7 +91,7 @@ class LocalNodeSource(SnapshotSource):
 
     def __init__(self, devices=None, source: str = "auto", counters: str = "auto", cfg=None,
                  window_buckets: int | None = None, window_trend: int | None = None, window_excursions=None,
-                 replay=None):
+                 replay=None, window_heatmap=None):
         """``window_buckets`` = B > 0 (default: ``ROCMDASH_WINDOW_BUCKETS``, else off): also
         export every series' window as B cumulative le-buckets + ``+Inf``
         (``rocmdash_window_bucket``; GpuAgent.window_buckets) and their sum over the GPUs -
@@ -102,7 +102,11 @@ class LocalNodeSource(SnapshotSource):
         ``window_excursions`` = ``"F1,F2,.."`` or a sequence of 1 to 4 increasing fractions in
         (0, 1] (default: ``ROCMDASH_WINDOW_EXCURSIONS``, else off): also export every series'
         episodes above those fractions of its axis (``rocmdash_window_excursions`` and its
-        neighbours; GpuAgent.window_excursions). ``replay``: the recording of ``source="replay"``."""
+        neighbours; GpuAgent.window_excursions). ``replay``: the recording of ``source="replay"``.
+        ``window_heatmap`` = ``"PxB"`` or ``(P, B)`` (default: ``ROCMDASH_WINDOW_HEATMAP``, else
+        off): the snapshot also carries every series' window as P + 1 columns of B + 1 bin
+        counts (GpuAgent.window_heatmap), served as JSON by ``GET /heatmap`` - never in
+        ``/metrics``."""
         from ..runtime import native
 
         if window_excursions is None:
@@ -121,6 +125,16 @@ class LocalNodeSource(SnapshotSource):
             from ..ops.window_trend import check_columns
 
             check_columns(self.trend_columns, (cfg or SamplerConfig()).window)
+        if window_heatmap is None:
+            window_heatmap = os.environ.get("ROCMDASH_WINDOW_HEATMAP", "") or None
+        self.heatmap = None
+        if window_heatmap is not None:  # checked before any agent starts its samplers
+            from ..config import SamplerConfig
+            from ..ops.window_heatmap import parse_heatmap
+            from ..ops.window_trend import check_columns
+
+            self.heatmap = parse_heatmap(window_heatmap)
+            check_columns(self.heatmap[0], (cfg or SamplerConfig()).window)
         native.load()
         if counters in ("auto", "hw"):
             native.enable_counters()
@@ -151,6 +165,8 @@ class LocalNodeSource(SnapshotSource):
         # likewise one set of thresholds for the node
         self.excursion_thresholds = (self.agents[0].default_excursion_thresholds(self.excursion_fractions)
                                      if self.excursion_fractions else None)
+        # and one set of heatmap bounds
+        self.heatmap_bounds = self.agents[0].default_bucket_bounds(self.heatmap[1]) if self.heatmap else None
 
     def collect(self):
         import torch
@@ -168,6 +184,10 @@ class LocalNodeSource(SnapshotSource):
             excursions = None
             if self.excursion_thresholds is not None:
                 excursions = [a.window_excursions(self.excursion_thresholds) for a in self.agents]
+            heatmap = heat_age = None
+            if self.heatmap is not None:
+                heatmap = [a.window_heatmap(self.heatmap[0], self.heatmap_bounds) for a in self.agents]
+                heat_age = self.agents[0].trend_age_rows(self.heatmap[0])
             host = np.stack([o.to("cpu", non_blocking=False).numpy() for o in outs])
             if buckets is not None:
                 buckets = np.stack([b.to("cpu", non_blocking=False).numpy() for b in buckets])
@@ -175,6 +195,8 @@ class LocalNodeSource(SnapshotSource):
                 trend = np.stack([t.to("cpu", non_blocking=False).numpy() for t in trend])
             if excursions is not None:
                 excursions = np.stack([e.to("cpu", non_blocking=False).numpy() for e in excursions])
+            if heatmap is not None:
+                heatmap = np.stack([h.to("cpu", non_blocking=False).numpy() for h in heatmap])
             now_ns = time.time_ns()
             for i, a in enumerate(self.agents):
                 a.health_rows(self._health[i], now_ns)
@@ -206,6 +228,9 @@ class LocalNodeSource(SnapshotSource):
             snap.window_trend, snap.window_trend_age_rows = trend, age
         if excursions is not None:
             snap.window_excursions, snap.window_excursion_thresholds = excursions, self.excursion_thresholds
+        if heatmap is not None:
+            snap.window_heatmap, snap.window_heatmap_age_rows = heatmap, heat_age
+            snap.window_heatmap_bounds = np.broadcast_to(self.heatmap_bounds, (len(ids),) + self.heatmap_bounds.shape)
         exp = Exposition()
         for a, gid in zip(self.agents, ids):
             for sampler in a.samplers:
@@ -259,8 +284,29 @@ def render_trend(snap: NodeSnapshot) -> str | None:
     return json.dumps(doc, allow_nan=False)
 
 
+def render_heatmap(snap: NodeSnapshot) -> str | None:
+    """The snapshot's window heatmap as the ``/heatmap`` document, None when it carries none:
+    ``{"columns": P, "buckets": B, "age_rows": [P + 1], "series": [...], "gpus": {gpu_id:
+    {metric: {"le": [B bounds], "counts": [[B + 1 ints] x (P + 1)]}}}}``, slot 0 the oldest;
+    counts are per bin (not cumulative), the last bin being everything above the last bound."""
+    heat = getattr(snap, "window_heatmap", None)
+    bounds = getattr(snap, "window_heatmap_bounds", None)
+    if heat is None or bounds is None:
+        return None
+    heat, bounds = np.asarray(heat), np.asarray(bounds)
+    series = list(snap.window_series)
+    gpus = {}
+    for g, gid in enumerate(snap.gpu_ids):
+        gpus[gid] = {m: {"le": [float(v) for v in bounds[g, s]], "counts": heat[g, s].tolist()}
+                     for s, m in enumerate(series)}
+    age = getattr(snap, "window_heatmap_age_rows", None)
+    doc = {"columns": int(heat.shape[2]) - 1, "buckets": int(heat.shape[3]) - 1,
+           "age_rows": _nullable(age) if age is not None else None, "series": series, "gpus": gpus}
+    return json.dumps(doc, allow_nan=False)
+
+
 class Exporter:
-    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``). With window buckets on,
+    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``, ``/heatmap``). With window buckets on,
     ``rocmdash_window_bucket`` / ``rocmdash_node_window_bucket`` carry exact integer counts
     for any window the source keeps: up to 32768 samples from the resident sorted windows,
     longer windows (up to 2^26) streamed from the device rings and printed from float64."""
@@ -311,6 +357,17 @@ class Exporter:
             log.exception("collect failed")
             return None
 
+    def heatmap(self) -> str | None:
+        """The ``/heatmap`` document of a fresh collection; None when the source has no window
+        heatmap (the option is off) or the collection failed."""
+        try:
+            snap, _ = self.source.collect()
+            return render_heatmap(snap)
+        except Exception:
+            self.errors += 1
+            log.exception("collect failed")
+            return None
+
     def health(self) -> tuple:
         """(ok, message) for /healthz: the source's own verdict when it has one (the
         node service reports unhealthy when its refresh loop stalls), else OK."""
@@ -343,6 +400,12 @@ class Exporter:
                     doc = exporter.trend()
                     if doc is None:
                         body, ctype, code = b"no window trend (start with --window-trend P)\n", "text/plain", 404
+                    else:
+                        body, ctype, code = doc.encode(), "application/json", 200
+                elif self.path.split("?")[0] == "/heatmap":
+                    doc = exporter.heatmap()
+                    if doc is None:
+                        body, ctype, code = b"no window heatmap (start with --window-heatmap PxB)\n", "text/plain", 404
                     else:
                         body, ctype, code = doc.encode(), "application/json", 200
                 elif self.path in ("/healthz", "/-/healthy"):
@@ -393,7 +456,17 @@ def main(argv=None) -> int:
     ap.add_argument("--window-excursions", default=None, metavar="F1,F2,..",
                     help="also export every series' episodes above these fractions of its axis: 1 to 4 increasing "
                          "fractions in (0, 1], e.g. 0.5,0.9 (default ROCMDASH_WINDOW_EXCURSIONS, else off)")
+    ap.add_argument("--window-heatmap", default=None, metavar="PxB",
+                    help="also serve GET /heatmap: every series' window as P + 1 columns of B + 1 bin counts, e.g. "
+                         "64x16 (P a power of two in 8..1024, B in 1..63; default ROCMDASH_WINDOW_HEATMAP, else off)")
     args = ap.parse_args(argv)
+    if args.window_heatmap is not None:
+        from ..ops.window_heatmap import parse_heatmap
+
+        try:
+            parse_heatmap(args.window_heatmap)
+        except ValueError as e:
+            ap.error(f"--window-heatmap: {e}")
     if args.window_excursions is not None:
         from ..ops.window_excursions import parse_fractions
 
@@ -404,7 +477,7 @@ def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO)
     src = SyntheticSource(args.synthetic) if args.synthetic else LocalNodeSource(
         source=args.source, counters=args.counters, window_buckets=args.window_buckets, window_trend=args.window_trend,
-        window_excursions=args.window_excursions, replay=args.replay)
+        window_excursions=args.window_excursions, replay=args.replay, window_heatmap=args.window_heatmap)
     exp = Exporter(src)
     exp.serve(args.host, args.port)
     log.info("serving /metrics on %s:%d", args.host, exp.port)

@@ -618,6 +618,51 @@ class GpuAgent:
         h = int(self.rings[ring_index].head)
         return trend_age_rows(h, min(h, self.window), self.window, int(columns))
 
+    def window_heatmap(self, columns: int = 64, bounds=None):
+        """Every series' window as a distribution over time, ``[S, columns + 1, B + 1]``
+        int32: per slot of ``window / columns`` rows (the slots of ``window_trend``) the
+        count of valid samples in each bin of ``bounds`` ([S, B] or [B]; default
+        ``default_bucket_bounds(16)``) - ``rocmdash.ops.window_heatmap`` states the
+        semantics; ``trend_age_rows`` gives the x axis. On a GPU the slots are counted from
+        the device rings the last ``refresh()`` left there (csrc/window_heatmap.hip), short
+        or long windows alike, in stream order; the bounds are uploaded once per bounds
+        object and the output is reused by the next call with the same columns and bounds."""
+        import torch
+
+        from ..ops.window_buckets import check_bounds
+        from ..ops.window_heatmap import DEFAULT_BUCKETS, window_heatmap_reference
+        from ..ops.window_trend import check_columns
+
+        P = int(columns)
+        check_columns(P, self.window)
+        if bounds is None:
+            bounds = getattr(self, "_default_heatmap_bounds", None)
+            if bounds is None:
+                bounds = self._default_heatmap_bounds = self.default_bucket_bounds(DEFAULT_BUCKETS)
+        S = len(self.series)
+        if self.dws is not None:
+            cached = getattr(self, "_heatmap", None)
+            if cached is None or cached[0] is not bounds or cached[2].shape[1] != P + 1:
+                b = check_bounds(bounds, S)
+                dev = cached[1] if cached is not None and cached[0] is bounds else torch.from_numpy(np.array(b)).to(self.device)
+                out = torch.empty((S, P + 1, b.shape[1] + 1), dtype=torch.int32, device=self.device)
+                cached = self._heatmap = (bounds, dev, out)
+            _, dev, out = cached
+            self.dws.export_heatmap(P, dev.data_ptr(), dev.shape[1], out.data_ptr(), _current_raw_stream(self.device_index))
+            return out
+        b = check_bounds(bounds, S)
+        out, s = np.empty((S, P + 1, b.shape[1] + 1), dtype=np.int32), 0
+        for r in self.rings:
+            for _ in range(8):  # the window and the head it ends at, with no row pushed in between
+                head = int(r.head)
+                rows, _ = r.window(self.window)
+                if int(r.head) == head:
+                    break
+            rows = np.asarray(rows, dtype=np.float32).reshape(-1, r.width)
+            out[s : s + r.width] = window_heatmap_reference(rows, head, self.window, P, b[s : s + r.width])
+            s += r.width
+        return torch.from_numpy(out)
+
     def default_excursion_thresholds(self, fractions=(0.5, 0.75, 0.9)) -> np.ndarray:
         """``[S, K]`` float32 thresholds of this GPU's series: ``fractions`` of each series'
         axis, the axis of ``default_bucket_bounds``

@@ -179,6 +179,39 @@ def window_trend_figures(snap: NodeSnapshot, selected=None, height: int = 220) -
     return figs
 
 
+def window_heatmap_figures(snap: NodeSnapshot, selected=None, height: int = 220) -> list | None:
+    """[(key, Figure)]: per selected GPU the window heatmap (``rocmdash.ops.window_heatmap``)
+    of every panel metric the snapshot's heatmap has - the metrics and the seconds of
+    ``window_trend_figures`` - as counts per bin over time (None if the snapshot carries no
+    heatmap)."""
+    heat = getattr(snap, "window_heatmap", None)
+    bounds = getattr(snap, "window_heatmap_bounds", None)
+    age = getattr(snap, "window_heatmap_age_rows", None)
+    if heat is None or bounds is None or age is None:
+        return None
+    from ..models.schema import CTR_FIELDS
+    from ..viz.figures import create_heatmap
+    from ..viz.panels import EXTENDED_PANELS, POWER, TEMP, UTIL
+
+    cfg = config.SamplerConfig()
+    index = {s: i for i, s in enumerate(snap.window_series)}
+    sel = set(str(g) for g in selected) if selected is not None else None
+    figs = []
+    for g, gid in enumerate(snap.gpu_ids):
+        if sel is not None and gid not in sel:
+            continue
+        panels = [(UTIL, "GPU Utilization (%)", "gpu_util"), (TEMP, "Temperature (°C)", "temp"),
+                  (POWER, "Power Usage (W)", "power")] + [p[:3] for p in EXTENDED_PANELS]
+        for col, title, key in panels:
+            s = index.get(col)
+            if s is None:
+                continue
+            period = 1.0 / (cfg.counter_hz if col in CTR_FIELDS else cfg.smi_hz)
+            figs.append((f"plot_heatmap_{key}_{gid}_", create_heatmap(f"GPU {gid}: {title}", [a * period for a in age],
+                                                                       bounds[g][s], heat[g, s], height)))
+    return figs
+
+
 def window_excursion_tables(snap: NodeSnapshot, selected=None) -> dict | None:
     """{"GPU <id>": [{metric, threshold, episodes, longest, current, since}, ...]}: per selected
     GPU one table of the window excursions (``rocmdash.ops.window_excursions``; lengths in
@@ -225,7 +258,8 @@ def xcd_table(snap: NodeSnapshot, selected=None) -> dict | None:
 
 
 def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xcd: dict | None = None,
-                  buckets: dict | None = None, trend: list | None = None, excursions: dict | None = None) -> None:
+                  buckets: dict | None = None, trend: list | None = None, excursions: dict | None = None,
+                  heatmap: list | None = None) -> None:
     st.subheader("Average Metrics (Selected GPUs)")
     avg_cols = st.columns(4)
     for col, (key, spec) in zip(avg_cols, frame.avg_panels):
@@ -260,6 +294,12 @@ def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xc
         st.subheader("Window Trend (min / max band and mean per column of the window)")
         for i in range(0, len(trend), 4):
             for col, (key, fig) in zip(st.columns(4), trend[i : i + 4]):
+                with col:
+                    st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
+    if extended and heatmap:
+        st.subheader("Window Heatmap (samples per bucket and column of the window)")
+        for i in range(0, len(heatmap), 4):
+            for col, (key, fig) in zip(st.columns(4), heatmap[i : i + 4]):
                 with col:
                     st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
     if extended and excursions:
@@ -338,7 +378,8 @@ def main(max_refreshes: int | None = None, data_source: str | None = None) -> No
                               xcd_table(snap, st.session_state.selected_gpus) if extended else None,
                               window_bucket_table(snap) if extended else None,
                               window_trend_figures(snap, st.session_state.selected_gpus) if extended else None,
-                              window_excursion_tables(snap, st.session_state.selected_gpus) if extended else None)
+                              window_excursion_tables(snap, st.session_state.selected_gpus) if extended else None,
+                              window_heatmap_figures(snap, st.session_state.selected_gpus) if extended else None)
         n += 1
         if max_refreshes is not None and n >= max_refreshes:
             break

@@ -440,6 +440,42 @@ def create_trend(title, age_s, lo, hi, mean, max_val=None, height=220) -> Figure
     return Figure(data, layout)
 
 
+def create_heatmap(title, age_s, le, counts, height=220) -> Figure:
+    """A window heatmap (``rocmdash.ops.window_heatmap``) as one Plotly ``heatmap`` trace:
+    x = seconds before the newest sample (negative: time runs left to right), y = each bin's
+    upper bound, z = the counts. ``age_s``: one entry per slot, oldest first; ``le``: the B
+    bounds; ``counts``: ``[slots][B + 1]`` per-bin counts. A slot whose age is NaN or that
+    holds no valid sample (empty) is a null column - a gap, never a column of zeroes. The top
+    bin (everything above the last bound, the axis maximum) has no upper bound of its own: it
+    is drawn one bin width above the axis maximum and labelled ``> maximum``. No reference
+    counterpart."""
+    le = [_num(v) for v in le]
+    B = len(le)
+    step = le[-1] - le[-2] if B > 1 else (abs(le[-1]) or 1.0)
+    ys = le + [le[-1] + step]
+    xs, cols = [], []
+    for a, c in zip(age_s, counts):
+        a, c = _num(a), [int(v) for v in c]
+        gap = a is None or not any(c)
+        xs.append(None if a is None else -a)
+        cols.append([None] * (B + 1) if gap else c)
+    z = [[col[k] for col in cols] for k in range(B + 1)]  # rows of z are bins
+    every = max(1, -(-B // 16))  # at most ~16 labelled bounds, and always the top bin
+    ticks = list(range(every - 1, B, every))
+    trace = {"colorbar": {"title": {"text": "samples"}}, "hoverongaps": False, "x": xs, "y": ys, "z": z, "zmin": 0,
+             "type": "heatmap"}
+    layout = {
+        "title": {"text": title},
+        "xaxis": {"title": {"text": "seconds"}},
+        "yaxis": {"tickmode": "array", "tickvals": [ys[k] for k in ticks] + [ys[B]],
+                  "ticktext": [f"{le[k]:g}" for k in ticks] + [f"> {le[-1]:g}"]},
+        "margin": {"l": 40, "r": 20, "t": 40, "b": 40},
+        "height": _num(height),
+        "showlegend": False,
+    }
+    return Figure([trace], layout)
+
+
 def create_chart(value, title, max_val, height, use_gauge=True) -> Figure:
     """Style dispatch without any UI-framework state (the app layer supplies
     ``use_gauge`` from the session, app.py:242-245)."""

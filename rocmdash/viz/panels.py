@@ -117,6 +117,12 @@ class NodeSnapshot:
     # per threshold of window_excursion_thresholds [S, K]
     window_excursions: np.ndarray | None = None
     window_excursion_thresholds: np.ndarray | None = None
+    # Window heatmap (rocmdash.ops.window_heatmap), when computed: per GPU
+    # [N, S, P + 1, B + 1] int32 - the per-bin counts of each of the trend's P + 1 column
+    # slots over window_heatmap_bounds [N, S, B] - and the slots' ages as for the trend
+    window_heatmap: np.ndarray | None = None
+    window_heatmap_bounds: np.ndarray | None = None
+    window_heatmap_age_rows: np.ndarray | None = None
 
     def __post_init__(self):
         self.values = np.asarray(self.values, dtype=np.float64)
