@@ -17,6 +17,7 @@
 #include "window_buckets.h"
 #include "window_excursions.h"
 #include "window_heatmap.h"
+#include "window_joint.h"
 #include "window_trend.h"
 
 namespace rocmdash {
@@ -381,6 +382,26 @@ PYBIND11_MODULE(_native, m) {
           "Enqueue every series' window trend after the last refresh: dst [S][columns + 1][4] floats "
           "(min, max, mean, count per slot of window / columns rows).")
       .def(
+          "export_joint",
+          [](LongWindowSet& w, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uintptr_t bounds, uint32_t B,
+             uintptr_t dst, uintptr_t stream) {
+            std::vector<uint32_t> flat;
+            for (const auto& p : pairs) {
+              flat.push_back(p.first);
+              flat.push_back(p.second);
+            }
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_joint(flat.data(), uint32_t(pairs.size()), reinterpret_cast<const float*>(bounds), B,
+                                 reinterpret_cast<int32_t*>(dst), reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_joint failed: " + std::to_string(e));
+          },
+          py::arg("pairs"), py::arg("bounds_ptr"), py::arg("num_bounds"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue the joint histograms of pairs [(a, b), ..] of series of one ring after the last refresh: bounds "
+          "[S][B] floats -> dst [K][B + 1][B + 1] int32 (rows with bin(x_a) == i and bin(x_b) == j, both valid).")
+      .def(
           "export_heatmap",
           [](LongWindowSet& w, uint32_t P, uintptr_t bounds, uint32_t B, uintptr_t dst, uintptr_t stream) {
             int e;
@@ -551,6 +572,26 @@ PYBIND11_MODULE(_native, m) {
           py::arg("columns"), py::arg("dst_ptr"), py::arg("stream"),
           "Enqueue every series' window trend after the last refresh: dst [S][columns + 1][4] floats "
           "(min, max, mean, count per slot of window / columns rows).")
+      .def(
+          "export_joint",
+          [](const DeviceWindowSet& w, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uintptr_t bounds, uint32_t B,
+             uintptr_t dst, uintptr_t stream) {
+            std::vector<uint32_t> flat;
+            for (const auto& p : pairs) {
+              flat.push_back(p.first);
+              flat.push_back(p.second);
+            }
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_joint(flat.data(), uint32_t(pairs.size()), reinterpret_cast<const float*>(bounds), B,
+                                 reinterpret_cast<int32_t*>(dst), reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_joint failed: " + std::to_string(e));
+          },
+          py::arg("pairs"), py::arg("bounds_ptr"), py::arg("num_bounds"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue the joint histograms of pairs [(a, b), ..] of series of one ring after the last refresh: bounds "
+          "[S][B] floats -> dst [K][B + 1][B + 1] int32 (rows with bin(x_a) == i and bin(x_b) == j, both valid).")
       .def(
           "export_heatmap",
           [](const DeviceWindowSet& w, uint32_t P, uintptr_t bounds, uint32_t B, uintptr_t dst, uintptr_t stream) {
@@ -891,6 +932,29 @@ PYBIND11_MODULE(_native, m) {
       py::arg("stream"),
       "Window heatmap of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) whose window is rows "
       "[head - n, head): bounds [cols][B] floats -> dst [cols][columns + 1][B + 1] int32 (per-bin counts per slot).");
+  m.def(
+      "joint_ring",
+      [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n,
+         const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uintptr_t bounds, uint32_t B, uintptr_t dst,
+         uintptr_t stream) {
+        std::vector<uint32_t> flat;
+        for (const auto& p : pairs) {
+          flat.push_back(p.first);
+          flat.push_back(p.second);
+        }
+        int e;
+        {
+          py::gil_scoped_release nogil;
+          e = launch_joint_ring(reinterpret_cast<const float*>(base), stride, cols, depth, head, n, flat.data(),
+                                uint32_t(pairs.size()), reinterpret_cast<const float*>(bounds), B,
+                                reinterpret_cast<int32_t*>(dst), reinterpret_cast<void*>(stream));
+        }
+        if (e != 0) throw std::runtime_error("joint_ring failed: " + std::to_string(e));
+      },
+      py::arg("base_ptr"), py::arg("stride"), py::arg("cols"), py::arg("depth"), py::arg("head"), py::arg("n"),
+      py::arg("pairs"), py::arg("bounds_ptr"), py::arg("num_bounds"), py::arg("dst_ptr"), py::arg("stream"),
+      "Joint histograms of pairs [(a, b), ..] of columns of one time-major ring [depth][stride] (row r at slot r & "
+      "(depth - 1)) whose window is rows [head - n, head): bounds [cols][B] floats -> dst [K][B + 1][B + 1] int32.");
 
   // ---- native frame renderer (csrc/frame_render.h) ---------------------------------
   py::class_<FramePlan, std::shared_ptr<FramePlan>>(m, "FramePlan")

@@ -103,6 +103,14 @@ class DeviceWindowSet {
   // first refresh and after invalidate()). Returns a hipError_t (hipErrorInvalidValue before
   // any launch or write for a bad argument).
   int export_heatmap(uint32_t P, const float* bounds, uint32_t B, int32_t* dst, void* stream) const;
+  // Enqueue, after the refresh that produced it, the joint histograms of K pairs of series
+  // (window_joint.h, defined in window_joint.hip) over the window of the last refresh: pairs
+  // HOST [K][2] series indices of this set, both of one ring and a != b; bounds device
+  // [num_series][B] (as export_buckets), 1 <= B <= 31; dst device [K][B + 1][B + 1] int32,
+  // every cell written (all zeroes before the first refresh and after invalidate()). A ring
+  // without a pair is not streamed. Returns a hipError_t (hipErrorInvalidValue before any
+  // launch or write for a bad argument, a pair across rings included).
+  int export_joint(const uint32_t* pairs, uint32_t K, const float* bounds, uint32_t B, int32_t* dst, void* stream) const;
   // Enqueue, after the refresh that produced it, every series' window excursions
   // (window_excursions.h, defined in window_excursions.hip) over the window of the last
   // refresh: thresholds device [num_series][K], dst device [num_series][K][8] int32 (all

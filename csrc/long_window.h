@@ -257,6 +257,12 @@ class LongWindowSet {
   // per-bin counts, every one written. Rows the host ring lost count as invalid. Returns a
   // hipError_t as export_trend does.
   int export_heatmap(uint32_t P, const float* bounds, uint32_t B, int32_t* dst, void* stream);
+  // Enqueue, after the refresh that left it on the device, the joint histograms of K pairs of
+  // series (window_joint.h, defined in window_joint.hip): pairs HOST [K][2] series indices of
+  // this set, both of one ring and a != b; bounds device [num_series][B], 1 <= B <= 31; dst
+  // device [K][B + 1][B + 1] int32, every cell written. A ring without a pair is not
+  // streamed. Returns a hipError_t as export_buckets does.
+  int export_joint(const uint32_t* pairs, uint32_t K, const float* bounds, uint32_t B, int32_t* dst, void* stream);
   // Enqueue, after the refresh that left it on the device, every series' cumulative
   // le-buckets (long_window_buckets.h, defined in long_window_buckets.hip): bounds device
   // [num_series][B], dst device [num_series][B + 1] doubles, series in set order. One

@@ -91,7 +91,7 @@ class LocalNodeSource(SnapshotSource):
 
     def __init__(self, devices=None, source: str = "auto", counters: str = "auto", cfg=None,
                  window_buckets: int | None = None, window_trend: int | None = None, window_excursions=None,
-                 replay=None, window_heatmap=None):
+                 replay=None, window_heatmap=None, window_joint=None):
         """``window_buckets`` = B > 0 (default: ``ROCMDASH_WINDOW_BUCKETS``, else off): also
         export every series' window as B cumulative le-buckets + ``+Inf``
         (``rocmdash_window_bucket``; GpuAgent.window_buckets) and their sum over the GPUs -
@@ -106,7 +106,11 @@ class LocalNodeSource(SnapshotSource):
         ``window_heatmap`` = ``"PxB"`` or ``(P, B)`` (default: ``ROCMDASH_WINDOW_HEATMAP``, else
         off): the snapshot also carries every series' window as P + 1 columns of B + 1 bin
         counts (GpuAgent.window_heatmap), served as JSON by ``GET /heatmap`` - never in
-        ``/metrics``."""
+        ``/metrics``. ``window_joint`` = ``"default"`` or ``"metricA:metricB,.."`` with an
+        optional ``/B`` (``rocmdash.ops.window_joint.parse_joint``; default:
+        ``ROCMDASH_WINDOW_JOINT``, else off): the snapshot also carries the joint histograms of
+        those pairs of series (GpuAgent.window_joint), served as JSON by ``GET /joint`` - never
+        in ``/metrics``."""
         from ..runtime import native
 
         if window_excursions is None:
@@ -135,6 +139,13 @@ class LocalNodeSource(SnapshotSource):
 
             self.heatmap = parse_heatmap(window_heatmap)
             check_columns(self.heatmap[0], (cfg or SamplerConfig()).window)
+        if window_joint is None:
+            window_joint = os.environ.get("ROCMDASH_WINDOW_JOINT", "") or None
+        if window_joint is not None:  # the spec, its metrics and its rings: checked before any agent exists
+            from ..models.schema import CTR_FIELDS, SMI_FIELDS
+            from ..ops.window_joint import parse_joint
+
+            parse_joint(window_joint, SMI_FIELDS + CTR_FIELDS, (len(SMI_FIELDS), len(CTR_FIELDS)))
         native.load()
         if counters in ("auto", "hw"):
             native.enable_counters()
@@ -152,6 +163,15 @@ class LocalNodeSource(SnapshotSource):
         if len(series) != 1:
             raise RuntimeError(f"GPUs disagree on the series layout: {series}")
         self.series = self.agents[0].series
+        self.joint = None  # (pairs, B): against the series these GPUs have, still before any sampler starts
+        if window_joint is not None:
+            from ..ops.window_joint import parse_joint
+
+            try:
+                self.joint = parse_joint(window_joint, self.series, [r.width for r in self.agents[0].rings])
+            except ValueError:
+                self.close()
+                raise
         for a in self.agents:
             a.start()
         self._lock = threading.Lock()
@@ -167,6 +187,8 @@ class LocalNodeSource(SnapshotSource):
                                      if self.excursion_fractions else None)
         # and one set of heatmap bounds
         self.heatmap_bounds = self.agents[0].default_bucket_bounds(self.heatmap[1]) if self.heatmap else None
+        # and one set of joint bounds
+        self.joint_bounds = self.agents[0].default_bucket_bounds(self.joint[1]) if self.joint else None
 
     def collect(self):
         import torch
@@ -188,6 +210,9 @@ class LocalNodeSource(SnapshotSource):
             if self.heatmap is not None:
                 heatmap = [a.window_heatmap(self.heatmap[0], self.heatmap_bounds) for a in self.agents]
                 heat_age = self.agents[0].trend_age_rows(self.heatmap[0])
+            joint = None
+            if self.joint is not None:
+                joint = [a.window_joint(self.joint[0], self.joint_bounds) for a in self.agents]
             host = np.stack([o.to("cpu", non_blocking=False).numpy() for o in outs])
             if buckets is not None:
                 buckets = np.stack([b.to("cpu", non_blocking=False).numpy() for b in buckets])
@@ -197,6 +222,8 @@ class LocalNodeSource(SnapshotSource):
                 excursions = np.stack([e.to("cpu", non_blocking=False).numpy() for e in excursions])
             if heatmap is not None:
                 heatmap = np.stack([h.to("cpu", non_blocking=False).numpy() for h in heatmap])
+            if joint is not None:
+                joint = np.stack([j.to("cpu", non_blocking=False).numpy() for j in joint])
             now_ns = time.time_ns()
             for i, a in enumerate(self.agents):
                 a.health_rows(self._health[i], now_ns)
@@ -231,6 +258,9 @@ class LocalNodeSource(SnapshotSource):
         if heatmap is not None:
             snap.window_heatmap, snap.window_heatmap_age_rows = heatmap, heat_age
             snap.window_heatmap_bounds = np.broadcast_to(self.heatmap_bounds, (len(ids),) + self.heatmap_bounds.shape)
+        if joint is not None:
+            snap.window_joint, snap.window_joint_pairs = joint, tuple(self.joint[0])
+            snap.window_joint_bounds = np.broadcast_to(self.joint_bounds, (len(ids),) + self.joint_bounds.shape)
         exp = Exposition()
         for a, gid in zip(self.agents, ids):
             for sampler in a.samplers:
@@ -305,8 +335,30 @@ def render_heatmap(snap: NodeSnapshot) -> str | None:
     return json.dumps(doc, allow_nan=False)
 
 
+def render_joint(snap: NodeSnapshot) -> str | None:
+    """The snapshot's window joint histograms as the ``/joint`` document, None when it carries
+    none: ``{"buckets": B, "pairs": [[x, y], ..], "gpus": {gpu_id: [{"x": name, "y": name,
+    "le_x": [B], "le_y": [B], "counts": [[B + 1] x (B + 1)], "rows": sum}, ..]}}``;
+    ``counts[i][j]`` is the number of rows with x in bin i and y in bin j (per bin, the last
+    being everything above the last bound), ``rows`` the rows in which both were valid."""
+    joint = getattr(snap, "window_joint", None)
+    pairs = getattr(snap, "window_joint_pairs", None)
+    bounds = getattr(snap, "window_joint_bounds", None)
+    if joint is None or pairs is None or bounds is None:
+        return None
+    joint, bounds = np.asarray(joint), np.asarray(bounds)
+    series = list(snap.window_series)
+    gpus = {}
+    for g, gid in enumerate(snap.gpu_ids):
+        gpus[gid] = [{"x": series[a], "y": series[b], "le_x": [float(v) for v in bounds[g, a]],
+                      "le_y": [float(v) for v in bounds[g, b]], "counts": joint[g, k].tolist(),
+                      "rows": int(joint[g, k].sum())} for k, (a, b) in enumerate(pairs)]
+    doc = {"buckets": int(joint.shape[2]) - 1, "pairs": [[series[a], series[b]] for a, b in pairs], "gpus": gpus}
+    return json.dumps(doc, allow_nan=False)
+
+
 class Exporter:
-    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``, ``/heatmap``). With window buckets on,
+    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``, ``/heatmap``, ``/joint``). With window buckets on,
     ``rocmdash_window_bucket`` / ``rocmdash_node_window_bucket`` carry exact integer counts
     for any window the source keeps: up to 32768 samples from the resident sorted windows,
     longer windows (up to 2^26) streamed from the device rings and printed from float64."""
@@ -368,6 +420,17 @@ class Exporter:
             log.exception("collect failed")
             return None
 
+    def joint(self) -> str | None:
+        """The ``/joint`` document of a fresh collection; None when the source has no window
+        joint histogram (the option is off) or the collection failed."""
+        try:
+            snap, _ = self.source.collect()
+            return render_joint(snap)
+        except Exception:
+            self.errors += 1
+            log.exception("collect failed")
+            return None
+
     def health(self) -> tuple:
         """(ok, message) for /healthz: the source's own verdict when it has one (the
         node service reports unhealthy when its refresh loop stalls), else OK."""
@@ -406,6 +469,12 @@ class Exporter:
                     doc = exporter.heatmap()
                     if doc is None:
                         body, ctype, code = b"no window heatmap (start with --window-heatmap PxB)\n", "text/plain", 404
+                    else:
+                        body, ctype, code = doc.encode(), "application/json", 200
+                elif self.path.split("?")[0] == "/joint":
+                    doc = exporter.joint()
+                    if doc is None:
+                        body, ctype, code = b"no window joint histogram (start with --window-joint SPEC)\n", "text/plain", 404
                     else:
                         body, ctype, code = doc.encode(), "application/json", 200
                 elif self.path in ("/healthz", "/-/healthy"):
@@ -459,7 +528,19 @@ def main(argv=None) -> int:
     ap.add_argument("--window-heatmap", default=None, metavar="PxB",
                     help="also serve GET /heatmap: every series' window as P + 1 columns of B + 1 bin counts, e.g. "
                          "64x16 (P a power of two in 8..1024, B in 1..63; default ROCMDASH_WINDOW_HEATMAP, else off)")
+    ap.add_argument("--window-joint", default=None, metavar="SPEC",
+                    help="also serve GET /joint: joint histograms of pairs of series of one ring; SPEC is 'default' or "
+                         "comma-separated metricA:metricB (amd_gpu_ optional), 1 to 8 pairs, with an optional /B "
+                         "(buckets per axis, 1..31, default 16) (default ROCMDASH_WINDOW_JOINT, else off)")
     args = ap.parse_args(argv)
+    if args.window_joint is not None:
+        from ..models.schema import CTR_FIELDS, SMI_FIELDS
+        from ..ops.window_joint import parse_joint
+
+        try:
+            parse_joint(args.window_joint, SMI_FIELDS + CTR_FIELDS, (len(SMI_FIELDS), len(CTR_FIELDS)))
+        except ValueError as e:
+            ap.error(f"--window-joint: {e}")
     if args.window_heatmap is not None:
         from ..ops.window_heatmap import parse_heatmap
 
@@ -477,7 +558,8 @@ def main(argv=None) -> int:
     logging.basicConfig(level=logging.INFO)
     src = SyntheticSource(args.synthetic) if args.synthetic else LocalNodeSource(
         source=args.source, counters=args.counters, window_buckets=args.window_buckets, window_trend=args.window_trend,
-        window_excursions=args.window_excursions, replay=args.replay, window_heatmap=args.window_heatmap)
+        window_excursions=args.window_excursions, replay=args.replay, window_heatmap=args.window_heatmap,
+        window_joint=args.window_joint)
     exp = Exporter(src)
     exp.serve(args.host, args.port)
     log.info("serving /metrics on %s:%d", args.host, exp.port)

@@ -663,6 +663,64 @@ class GpuAgent:
             s += r.width
         return torch.from_numpy(out)
 
+    def default_joint_pairs(self) -> list:
+        """``[(a, b), ..]`` series indices: those of ``rocmdash.ops.window_joint.DEFAULT_PAIRS``
+        whose two series this GPU has (without a counter ring the MFMA / HBM pairs are left
+        out). Each pair lies in one ring."""
+        from ..ops.window_joint import DEFAULT_PAIRS, PREFIX
+
+        index = {s: i for i, s in enumerate(self.series)}
+        return [(index[PREFIX + a], index[PREFIX + b]) for a, b in DEFAULT_PAIRS
+                if PREFIX + a in index and PREFIX + b in index]
+
+    def window_joint(self, pairs=None, bounds=None):
+        """Joint histograms of pairs of this GPU's series, ``[K, B + 1, B + 1]`` int32:
+        ``out[k][i][j]`` is the number of rows of the window in which series ``a`` of pair k
+        lay in bin i and series ``b`` in bin j of ``bounds`` ([S, B] or [B], B <= 31; default
+        ``default_bucket_bounds(16)``), both valid - ``rocmdash.ops.window_joint`` states the
+        semantics. ``pairs``: ``[(a, b), ..]`` series indices, both of one ring (default
+        ``default_joint_pairs()``). On a GPU the rows are counted from the device rings the
+        last ``refresh()`` left there (csrc/window_joint.hip), short or long windows alike, in
+        stream order; the bounds are uploaded once per bounds object and the output is reused
+        by the next call with the same pairs and the same bounds object."""
+        import torch
+
+        from ..ops.window_joint import DEFAULT_BUCKETS, check_joint_bounds, check_pairs, window_joint_reference
+
+        if pairs is None:
+            pairs = getattr(self, "_default_joint_pairs", None)
+            if pairs is None:
+                pairs = self._default_joint_pairs = self.default_joint_pairs()
+        if bounds is None:
+            bounds = getattr(self, "_default_joint_bounds", None)
+            if bounds is None:
+                bounds = self._default_joint_bounds = self.default_bucket_bounds(DEFAULT_BUCKETS)
+        S = len(self.series)
+        widths = [r.width for r in self.rings]
+        if self.dws is not None:
+            checked = check_pairs(pairs, widths)  # at most 8: compared by value, so a fresh list reuses the buffer
+            cached = getattr(self, "_joint", None)
+            if cached is None or cached[0] != checked or cached[1] is not bounds:
+                b = check_joint_bounds(bounds, S)
+                dev = cached[2] if cached is not None and cached[1] is bounds else torch.from_numpy(np.array(b)).to(self.device)
+                out = torch.empty((len(checked), b.shape[1] + 1, b.shape[1] + 1), dtype=torch.int32, device=self.device)
+                cached = self._joint = (checked, bounds, dev, out)
+            _, _, dev, out = cached
+            self.dws.export_joint(checked, dev.data_ptr(), dev.shape[1], out.data_ptr(), _current_raw_stream(self.device_index))
+            return out
+        checked = check_pairs(pairs, widths)
+        b = check_joint_bounds(bounds, S)
+        out, s = np.zeros((len(checked), b.shape[1] + 1, b.shape[1] + 1), dtype=np.int32), 0
+        for r in self.rings:
+            mine = [k for k, (a, _) in enumerate(checked) if s <= a < s + r.width]
+            if mine:
+                rows, _ = r.window(self.window)
+                rows = np.asarray(rows, dtype=np.float32).reshape(-1, r.width)
+                out[mine] = window_joint_reference(rows, [(checked[k][0] - s, checked[k][1] - s) for k in mine],
+                                                   b[s : s + r.width])
+            s += r.width
+        return torch.from_numpy(out)
+
     def default_excursion_thresholds(self, fractions=(0.5, 0.75, 0.9)) -> np.ndarray:
         """``[S, K]`` float32 thresholds of this GPU's series: ``fractions`` of each series'
         axis, the axis of ``default_bucket_bounds``

@@ -212,6 +212,31 @@ def window_heatmap_figures(snap: NodeSnapshot, selected=None, height: int = 220)
     return figs
 
 
+def window_joint_figures(snap: NodeSnapshot, selected=None, height: int = 260) -> list | None:
+    """[(key, Figure)]: per selected GPU and pair the window joint histogram
+    (``rocmdash.ops.window_joint``) the snapshot carries - the first series on x, the second on
+    y, rows as colour (None if the snapshot carries none)."""
+    joint = getattr(snap, "window_joint", None)
+    pairs = getattr(snap, "window_joint_pairs", None)
+    bounds = getattr(snap, "window_joint_bounds", None)
+    if joint is None or pairs is None or bounds is None:
+        return None
+    from ..viz.figures import create_joint
+
+    series = list(snap.window_series)
+    short = lambda m: m[len("amd_gpu_"):] if m.startswith("amd_gpu_") else m  # noqa: E731
+    sel = set(str(g) for g in selected) if selected is not None else None
+    figs = []
+    for g, gid in enumerate(snap.gpu_ids):
+        if sel is not None and gid not in sel:
+            continue
+        for k, (a, b) in enumerate(pairs):
+            x, y = short(series[a]), short(series[b])
+            figs.append((f"plot_joint_{x}_{y}_{gid}_", create_joint(f"GPU {gid}: {y} vs {x}", bounds[g][a], bounds[g][b],
+                                                                     joint[g][k], x, y, height)))
+    return figs
+
+
 def window_excursion_tables(snap: NodeSnapshot, selected=None) -> dict | None:
     """{"GPU <id>": [{metric, threshold, episodes, longest, current, since}, ...]}: per selected
     GPU one table of the window excursions (``rocmdash.ops.window_excursions``; lengths in
@@ -259,7 +284,7 @@ def xcd_table(snap: NodeSnapshot, selected=None) -> dict | None:
 
 def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xcd: dict | None = None,
                   buckets: dict | None = None, trend: list | None = None, excursions: dict | None = None,
-                  heatmap: list | None = None) -> None:
+                  heatmap: list | None = None, joint: list | None = None) -> None:
     st.subheader("Average Metrics (Selected GPUs)")
     avg_cols = st.columns(4)
     for col, (key, spec) in zip(avg_cols, frame.avg_panels):
@@ -300,6 +325,12 @@ def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xc
         st.subheader("Window Heatmap (samples per bucket and column of the window)")
         for i in range(0, len(heatmap), 4):
             for col, (key, fig) in zip(st.columns(4), heatmap[i : i + 4]):
+                with col:
+                    st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
+    if extended and joint:
+        st.subheader("Window Joint Histograms (rows per pair of buckets of two series)")
+        for i in range(0, len(joint), 4):
+            for col, (key, fig) in zip(st.columns(4), joint[i : i + 4]):
                 with col:
                     st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
     if extended and excursions:
@@ -379,7 +410,8 @@ def main(max_refreshes: int | None = None, data_source: str | None = None) -> No
                               window_bucket_table(snap) if extended else None,
                               window_trend_figures(snap, st.session_state.selected_gpus) if extended else None,
                               window_excursion_tables(snap, st.session_state.selected_gpus) if extended else None,
-                              window_heatmap_figures(snap, st.session_state.selected_gpus) if extended else None)
+                              window_heatmap_figures(snap, st.session_state.selected_gpus) if extended else None,
+                              window_joint_figures(snap, st.session_state.selected_gpus) if extended else None)
         n += 1
         if max_refreshes is not None and n >= max_refreshes:
             break

@@ -476,6 +476,45 @@ def create_heatmap(title, age_s, le, counts, height=220) -> Figure:
     return Figure([trace], layout)
 
 
+def create_joint(title, le_x, le_y, counts, x_title=None, y_title=None, height=260) -> Figure:
+    """A window joint histogram (``rocmdash.ops.window_joint``) as one Plotly ``heatmap`` trace:
+    x = each bin's upper bound of the pair's first series, y = of its second, z = the rows in
+    the cell. ``le_x`` / ``le_y``: the B bounds of the two series; ``counts``: ``[B + 1][B + 1]``
+    with ``counts[i][j]`` the rows with x in bin i and y in bin j. A cell without a row is null
+    - a gap, never a zero. The top bin of either axis (everything above the last bound, the axis
+    maximum) is drawn as ``create_heatmap`` draws it: one bin width above the maximum and
+    labelled ``> maximum``. No reference counterpart."""
+
+    def axis(le, text):
+        le = [_num(v) for v in le]
+        B = len(le)
+        step = le[-1] - le[-2] if B > 1 else (abs(le[-1]) or 1.0)
+        vals = le + [le[-1] + step]
+        every = max(1, -(-B // 16))  # at most ~16 labelled bounds, and always the top bin
+        ticks = list(range(every - 1, B, every))
+        ax = {"tickmode": "array", "tickvals": [vals[k] for k in ticks] + [vals[B]],
+              "ticktext": [f"{le[k]:g}" for k in ticks] + [f"> {le[-1]:g}"]}
+        if text is not None:
+            ax["title"] = {"text": text}
+        return vals, ax
+
+    xs, xaxis = axis(le_x, x_title)
+    ys, yaxis = axis(le_y, y_title)
+    counts = [[int(v) for v in row] for row in counts]
+    z = [[counts[i][j] or None for i in range(len(xs))] for j in range(len(ys))]  # rows of z are y bins
+    trace = {"colorbar": {"title": {"text": "rows"}}, "hoverongaps": False, "x": xs, "y": ys, "z": z, "zmin": 0,
+             "type": "heatmap"}
+    layout = {
+        "title": {"text": title},
+        "xaxis": xaxis,
+        "yaxis": yaxis,
+        "margin": {"l": 40, "r": 20, "t": 40, "b": 40},
+        "height": _num(height),
+        "showlegend": False,
+    }
+    return Figure([trace], layout)
+
+
 def create_chart(value, title, max_val, height, use_gauge=True) -> Figure:
     """Style dispatch without any UI-framework state (the app layer supplies
     ``use_gauge`` from the session, app.py:242-245)."""

@@ -123,6 +123,12 @@ class NodeSnapshot:
     window_heatmap: np.ndarray | None = None
     window_heatmap_bounds: np.ndarray | None = None
     window_heatmap_age_rows: np.ndarray | None = None
+    # Window joint histograms (rocmdash.ops.window_joint), when computed: per GPU
+    # [N, K, B + 1, B + 1] int32 - rows with series a of pair k in bin i and series b in bin j -
+    # the K pairs as (a, b) indices into window_series, and the bounds [N, S, B]
+    window_joint: np.ndarray | None = None
+    window_joint_pairs: tuple | None = None
+    window_joint_bounds: np.ndarray | None = None
 
     def __post_init__(self):
         self.values = np.asarray(self.values, dtype=np.float64)
