@@ -18,6 +18,7 @@
 #include "window_excursions.h"
 #include "window_heatmap.h"
 #include "window_joint.h"
+#include "window_quantiles.h"
 #include "window_trend.h"
 
 namespace rocmdash {
@@ -382,6 +383,20 @@ PYBIND11_MODULE(_native, m) {
           "Enqueue every series' window trend after the last refresh: dst [S][columns + 1][4] floats "
           "(min, max, mean, count per slot of window / columns rows).")
       .def(
+          "export_quantiles",
+          [](LongWindowSet& w, uint32_t P, uintptr_t dst, uintptr_t stream, float p0, float p1, float p2) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_quantiles(P, p0, p1, p2, reinterpret_cast<float*>(dst), reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_quantiles failed: " + std::to_string(e));
+          },
+          py::arg("columns"), py::arg("dst_ptr"), py::arg("stream"), py::arg("p0") = 50.0f, py::arg("p1") = 90.0f,
+          py::arg("p2") = 99.0f,
+          "Enqueue every series' window quantile trend after the last refresh: dst [S][columns + 1][4] floats "
+          "(the three percentiles and the count per slot of window / columns rows).")
+      .def(
           "export_joint",
           [](LongWindowSet& w, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uintptr_t bounds, uint32_t B,
              uintptr_t dst, uintptr_t stream) {
@@ -572,6 +587,20 @@ PYBIND11_MODULE(_native, m) {
           py::arg("columns"), py::arg("dst_ptr"), py::arg("stream"),
           "Enqueue every series' window trend after the last refresh: dst [S][columns + 1][4] floats "
           "(min, max, mean, count per slot of window / columns rows).")
+      .def(
+          "export_quantiles",
+          [](const DeviceWindowSet& w, uint32_t P, uintptr_t dst, uintptr_t stream, float p0, float p1, float p2) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_quantiles(P, p0, p1, p2, reinterpret_cast<float*>(dst), reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_quantiles failed: " + std::to_string(e));
+          },
+          py::arg("columns"), py::arg("dst_ptr"), py::arg("stream"), py::arg("p0") = 50.0f, py::arg("p1") = 90.0f,
+          py::arg("p2") = 99.0f,
+          "Enqueue every series' window quantile trend after the last refresh: dst [S][columns + 1][4] floats "
+          "(the three percentiles and the count per slot of window / columns rows).")
       .def(
           "export_joint",
           [](const DeviceWindowSet& w, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uintptr_t bounds, uint32_t B,
@@ -914,6 +943,24 @@ PYBIND11_MODULE(_native, m) {
       py::arg("columns"), py::arg("rows_per_col"), py::arg("dst_ptr"), py::arg("stream"),
       "Window trend of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) whose window is rows "
       "[head - n, head): dst [cols][columns + 1][4] floats (min, max, mean, count per slot of rows_per_col rows).");
+  m.attr("QUANTILE_SORT_MAX_ROWS") = int(kQuantileSortMaxRows);  // rows per column: above, the radix select
+  m.def(
+      "quantile_ring",
+      [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n, uint32_t P,
+         uint32_t rows_per_col, uintptr_t dst, uintptr_t stream, float p0, float p1, float p2) {
+        int e;
+        {
+          py::gil_scoped_release nogil;
+          e = launch_quantile_ring(reinterpret_cast<const float*>(base), stride, cols, depth, head, n, P, rows_per_col, p0,
+                                   p1, p2, reinterpret_cast<float*>(dst), reinterpret_cast<void*>(stream));
+        }
+        if (e != 0) throw std::runtime_error("quantile_ring failed: " + std::to_string(e));
+      },
+      py::arg("base_ptr"), py::arg("stride"), py::arg("cols"), py::arg("depth"), py::arg("head"), py::arg("n"),
+      py::arg("columns"), py::arg("rows_per_col"), py::arg("dst_ptr"), py::arg("stream"), py::arg("p0") = 50.0f,
+      py::arg("p1") = 90.0f, py::arg("p2") = 99.0f,
+      "Window quantile trend of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) whose window is "
+      "rows [head - n, head): dst [cols][columns + 1][4] floats (three percentiles and the count per slot).");
   m.def(
       "heatmap_ring",
       [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n, uint32_t P,

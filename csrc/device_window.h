@@ -103,6 +103,13 @@ class DeviceWindowSet {
   // first refresh and after invalidate()). Returns a hipError_t (hipErrorInvalidValue before
   // any launch or write for a bad argument).
   int export_heatmap(uint32_t P, const float* bounds, uint32_t B, int32_t* dst, void* stream) const;
+  // Enqueue, after the refresh that produced it, every series' window quantile trend
+  // (window_quantiles.h, defined in window_quantiles.hip): the slots of export_trend, each
+  // with the percentiles p0, p1, p2 (finite, in [0, 100]) of its valid samples by the stats
+  // kernel's arithmetic; dst device [num_series][P + 1][4] = {p0, p1, p2, count} (count 0 and
+  // NaNs for an empty slot). Returns a hipError_t (hipErrorInvalidValue before any launch or
+  // write for a bad argument).
+  int export_quantiles(uint32_t P, float p0, float p1, float p2, float* dst, void* stream) const;
   // Enqueue, after the refresh that produced it, the joint histograms of K pairs of series
   // (window_joint.h, defined in window_joint.hip) over the window of the last refresh: pairs
   // HOST [K][2] series indices of this set, both of one ring and a != b; bounds device

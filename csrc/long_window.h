@@ -257,6 +257,12 @@ class LongWindowSet {
   // per-bin counts, every one written. Rows the host ring lost count as invalid. Returns a
   // hipError_t as export_trend does.
   int export_heatmap(uint32_t P, const float* bounds, uint32_t B, int32_t* dst, void* stream);
+  // Enqueue, after the refresh that left it on the device, every series' window quantile
+  // trend (window_quantiles.h, defined in window_quantiles.hip): the slots of export_trend,
+  // each with the percentiles p0, p1, p2 (finite, in [0, 100]) of its valid samples; dst
+  // device [num_series][P + 1][4] = {p0, p1, p2, count}. Rows the host ring lost count as
+  // invalid. Returns a hipError_t as export_trend does.
+  int export_quantiles(uint32_t P, float p0, float p1, float p2, float* dst, void* stream);
   // Enqueue, after the refresh that left it on the device, the joint histograms of K pairs of
   // series (window_joint.h, defined in window_joint.hip): pairs HOST [K][2] series indices of
   // this set, both of one ring and a != b; bounds device [num_series][B], 1 <= B <= 31; dst

@@ -36,6 +36,7 @@ SOURCES = [
     "long_window_buckets.hip",
     "window_trend.hip",
     "window_heatmap.hip",
+    "window_quantiles.hip",
     "window_joint.hip",
     "window_excursions.hip",
     "calib.hip",

@@ -91,7 +91,7 @@ class LocalNodeSource(SnapshotSource):
 
     def __init__(self, devices=None, source: str = "auto", counters: str = "auto", cfg=None,
                  window_buckets: int | None = None, window_trend: int | None = None, window_excursions=None,
-                 replay=None, window_heatmap=None, window_joint=None):
+                 replay=None, window_heatmap=None, window_joint=None, window_quantiles: int | None = None):
         """``window_buckets`` = B > 0 (default: ``ROCMDASH_WINDOW_BUCKETS``, else off): also
         export every series' window as B cumulative le-buckets + ``+Inf``
         (``rocmdash_window_bucket``; GpuAgent.window_buckets) and their sum over the GPUs -
@@ -110,7 +110,10 @@ class LocalNodeSource(SnapshotSource):
         optional ``/B`` (``rocmdash.ops.window_joint.parse_joint``; default:
         ``ROCMDASH_WINDOW_JOINT``, else off): the snapshot also carries the joint histograms of
         those pairs of series (GpuAgent.window_joint), served as JSON by ``GET /joint`` - never
-        in ``/metrics``."""
+        in ``/metrics``. ``window_quantiles`` = P > 0 (default: ``ROCMDASH_WINDOW_QUANTILES``,
+        else off): the snapshot also carries every series' window as P + 1 columns of its three
+        percentiles and their count (GpuAgent.window_quantiles), served as JSON by
+        ``GET /quantiles`` - never in ``/metrics``."""
         from ..runtime import native
 
         if window_excursions is None:
@@ -129,6 +132,14 @@ class LocalNodeSource(SnapshotSource):
             from ..ops.window_trend import check_columns
 
             check_columns(self.trend_columns, (cfg or SamplerConfig()).window)
+        if window_quantiles is None:
+            window_quantiles = int(os.environ.get("ROCMDASH_WINDOW_QUANTILES", "0") or 0)
+        self.quantile_columns = int(window_quantiles) if window_quantiles else None
+        if self.quantile_columns is not None:  # checked before any agent starts its samplers
+            from ..config import SamplerConfig
+            from ..ops.window_quantiles import check_columns
+
+            check_columns(self.quantile_columns, (cfg or SamplerConfig()).window)
         if window_heatmap is None:
             window_heatmap = os.environ.get("ROCMDASH_WINDOW_HEATMAP", "") or None
         self.heatmap = None
@@ -213,6 +224,10 @@ class LocalNodeSource(SnapshotSource):
             joint = None
             if self.joint is not None:
                 joint = [a.window_joint(self.joint[0], self.joint_bounds) for a in self.agents]
+            quantiles = quant_age = None
+            if self.quantile_columns is not None:
+                quantiles = [a.window_quantiles(self.quantile_columns) for a in self.agents]
+                quant_age = self.agents[0].trend_age_rows(self.quantile_columns)
             host = np.stack([o.to("cpu", non_blocking=False).numpy() for o in outs])
             if buckets is not None:
                 buckets = np.stack([b.to("cpu", non_blocking=False).numpy() for b in buckets])
@@ -224,6 +239,8 @@ class LocalNodeSource(SnapshotSource):
                 heatmap = np.stack([h.to("cpu", non_blocking=False).numpy() for h in heatmap])
             if joint is not None:
                 joint = np.stack([j.to("cpu", non_blocking=False).numpy() for j in joint])
+            if quantiles is not None:
+                quantiles = np.stack([q.to("cpu", non_blocking=False).numpy() for q in quantiles])
             now_ns = time.time_ns()
             for i, a in enumerate(self.agents):
                 a.health_rows(self._health[i], now_ns)
@@ -261,6 +278,9 @@ class LocalNodeSource(SnapshotSource):
         if joint is not None:
             snap.window_joint, snap.window_joint_pairs = joint, tuple(self.joint[0])
             snap.window_joint_bounds = np.broadcast_to(self.joint_bounds, (len(ids),) + self.joint_bounds.shape)
+        if quantiles is not None:
+            snap.window_quantiles, snap.window_quantiles_age_rows = quantiles, quant_age
+            snap.window_quantiles_pct = tuple(self.agents[0].pct)
         exp = Exposition()
         for a, gid in zip(self.agents, ids):
             for sampler in a.samplers:
@@ -314,6 +334,32 @@ def render_trend(snap: NodeSnapshot) -> str | None:
     return json.dumps(doc, allow_nan=False)
 
 
+def quantile_keys(pct) -> list:
+    """The ``/quantiles`` document's key of each percentile: ``p50``, ``p99.9``."""
+    return [f"p{float(p):g}" for p in pct]
+
+
+def render_quantiles(snap: NodeSnapshot) -> str | None:
+    """The snapshot's window quantile trend as the ``/quantiles`` document, None when it carries
+    none: ``{"columns": P, "percentiles": [a, b, c], "age_rows": [P + 1], "series": [...],
+    "gpus": {gpu_id: {metric: {"p<a>": [P + 1], "p<b>": ..., "p<c>": ..., "count": ...}}}}``,
+    slot 0 the oldest, empty slots null."""
+    quant = getattr(snap, "window_quantiles", None)
+    pct = getattr(snap, "window_quantiles_pct", None)
+    if quant is None or pct is None:
+        return None
+    quant = np.asarray(quant)
+    series = list(snap.window_series)
+    keys = quantile_keys(pct) + ["count"]
+    gpus = {}
+    for g, gid in enumerate(snap.gpu_ids):
+        gpus[gid] = {m: {k: _nullable(quant[g, s, :, i]) for i, k in enumerate(keys)} for s, m in enumerate(series)}
+    age = getattr(snap, "window_quantiles_age_rows", None)
+    doc = {"columns": int(quant.shape[2]) - 1, "percentiles": [float(p) for p in pct],
+           "age_rows": _nullable(age) if age is not None else None, "series": series, "gpus": gpus}
+    return json.dumps(doc, allow_nan=False)
+
+
 def render_heatmap(snap: NodeSnapshot) -> str | None:
     """The snapshot's window heatmap as the ``/heatmap`` document, None when it carries none:
     ``{"columns": P, "buckets": B, "age_rows": [P + 1], "series": [...], "gpus": {gpu_id:
@@ -358,7 +404,7 @@ def render_joint(snap: NodeSnapshot) -> str | None:
 
 
 class Exporter:
-    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``, ``/heatmap``, ``/joint``). With window buckets on,
+    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``, ``/heatmap``, ``/joint``, ``/quantiles``). With window buckets on,
     ``rocmdash_window_bucket`` / ``rocmdash_node_window_bucket`` carry exact integer counts
     for any window the source keeps: up to 32768 samples from the resident sorted windows,
     longer windows (up to 2^26) streamed from the device rings and printed from float64."""
@@ -404,6 +450,17 @@ class Exporter:
         try:
             snap, _ = self.source.collect()
             return render_trend(snap)
+        except Exception:
+            self.errors += 1
+            log.exception("collect failed")
+            return None
+
+    def quantiles(self) -> str | None:
+        """The ``/quantiles`` document of a fresh collection; None when the source has no window
+        quantile trend (the option is off) or the collection failed."""
+        try:
+            snap, _ = self.source.collect()
+            return render_quantiles(snap)
         except Exception:
             self.errors += 1
             log.exception("collect failed")
@@ -477,6 +534,13 @@ class Exporter:
                         body, ctype, code = b"no window joint histogram (start with --window-joint SPEC)\n", "text/plain", 404
                     else:
                         body, ctype, code = doc.encode(), "application/json", 200
+                elif self.path.split("?")[0] == "/quantiles":
+                    doc = exporter.quantiles()
+                    if doc is None:
+                        body, ctype, code = (b"no window quantile trend (start with --window-quantiles P)\n", "text/plain",
+                                             404)
+                    else:
+                        body, ctype, code = doc.encode(), "application/json", 200
                 elif self.path in ("/healthz", "/-/healthy"):
                     ok, msg = exporter.health()
                     body, ctype, code = (msg + "\n").encode(), "text/plain", 200 if ok else 503
@@ -532,6 +596,9 @@ def main(argv=None) -> int:
                     help="also serve GET /joint: joint histograms of pairs of series of one ring; SPEC is 'default' or "
                          "comma-separated metricA:metricB (amd_gpu_ optional), 1 to 8 pairs, with an optional /B "
                          "(buckets per axis, 1..31, default 16) (default ROCMDASH_WINDOW_JOINT, else off)")
+    ap.add_argument("--window-quantiles", type=int, default=None, metavar="P",
+                    help="also serve GET /quantiles: every series' window as P + 1 columns of its exact percentiles "
+                         "and their count (a power of two in 8..1024; default ROCMDASH_WINDOW_QUANTILES, else off)")
     args = ap.parse_args(argv)
     if args.window_joint is not None:
         from ..models.schema import CTR_FIELDS, SMI_FIELDS
@@ -559,7 +626,7 @@ def main(argv=None) -> int:
     src = SyntheticSource(args.synthetic) if args.synthetic else LocalNodeSource(
         source=args.source, counters=args.counters, window_buckets=args.window_buckets, window_trend=args.window_trend,
         window_excursions=args.window_excursions, replay=args.replay, window_heatmap=args.window_heatmap,
-        window_joint=args.window_joint)
+        window_joint=args.window_joint, window_quantiles=args.window_quantiles)
     exp = Exporter(src)
     exp.serve(args.host, args.port)
     log.info("serving /metrics on %s:%d", args.host, exp.port)

@@ -610,6 +610,40 @@ class GpuAgent:
             s += r.width
         return torch.from_numpy(out)
 
+    def window_quantiles(self, columns: int = 128):
+        """Every series' percentiles over time, ``[S, columns + 1, 4]`` float32: per slot of
+        ``window / columns`` rows (the slots of ``window_trend``) the agent's three
+        percentiles (``self.pct``) of the slot's valid samples and their count
+        (``rocmdash.ops.window_quantiles`` states the semantics; ``trend_age_rows`` gives the
+        x axis). On a GPU the slots are selected from the device rings the last ``refresh()``
+        left there (csrc/window_quantiles.hip), short or long windows alike, in stream order,
+        into a buffer the next call with the same ``columns`` reuses."""
+        import torch
+
+        from ..ops.window_quantiles import check_columns, check_pct, window_quantiles_reference
+
+        P = int(columns)
+        check_columns(P, self.window)
+        pct = check_pct(self.pct)
+        S = len(self.series)
+        if self.dws is not None:
+            cached = getattr(self, "_quantiles_out", None)
+            if cached is None or cached.shape[1] != P + 1:
+                cached = self._quantiles_out = torch.empty((S, P + 1, 4), dtype=torch.float32, device=self.device)
+            self.dws.export_quantiles(P, cached.data_ptr(), _current_raw_stream(self.device_index), *pct)
+            return cached
+        out, s = np.empty((S, P + 1, 4), dtype=np.float32), 0
+        for r in self.rings:
+            for _ in range(8):  # the window and the head it ends at, with no row pushed in between
+                head = int(r.head)
+                rows, _ = r.window(self.window)
+                if int(r.head) == head:
+                    break
+            rows = np.asarray(rows, dtype=np.float32).reshape(-1, r.width)
+            out[s : s + r.width] = window_quantiles_reference(rows, head, self.window, P, pct)
+            s += r.width
+        return torch.from_numpy(out)
+
     def trend_age_rows(self, columns: int = 128, ring_index: int = 0) -> np.ndarray:
         """``[columns + 1]``: rows between each trend slot's last row and the newest row of
         ring ``ring_index`` (NaN: an empty slot), from the ring's head now."""

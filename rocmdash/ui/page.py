@@ -179,6 +179,41 @@ def window_trend_figures(snap: NodeSnapshot, selected=None, height: int = 220) -
     return figs
 
 
+def window_quantile_figures(snap: NodeSnapshot, selected=None, height: int = 220) -> list | None:
+    """[(key, Figure)]: per selected GPU the window quantile trend
+    (``rocmdash.ops.window_quantiles``) of every panel metric the snapshot's has - the metrics
+    and the seconds of ``window_trend_figures`` - as three percentile lines over time (None if
+    the snapshot carries none)."""
+    quant = getattr(snap, "window_quantiles", None)
+    age = getattr(snap, "window_quantiles_age_rows", None)
+    pct = getattr(snap, "window_quantiles_pct", None)
+    if quant is None or age is None or pct is None:
+        return None
+    from ..models.schema import CTR_FIELDS
+    from ..viz.figures import create_quantiles
+    from ..viz.panels import EXTENDED_PANELS, POWER, TEMP, UTIL
+
+    cfg = config.SamplerConfig()
+    index = {s: i for i, s in enumerate(snap.window_series)}
+    sel = set(str(g) for g in selected) if selected is not None else None
+    figs = []
+    for g, gid in enumerate(snap.gpu_ids):
+        if sel is not None and gid not in sel:
+            continue
+        panels = [(UTIL, "GPU Utilization (%)", "gpu_util", 100.0), (TEMP, "Temperature (°C)", "temp", 100.0),
+                  (POWER, "Power Usage (W)", "power", snap.power_max(gid))] + list(EXTENDED_PANELS)
+        for col, title, key, mx in panels:
+            s = index.get(col)
+            if s is None:
+                continue
+            period = 1.0 / (cfg.counter_hz if col in CTR_FIELDS else cfg.smi_hz)
+            q = quant[g, s]
+            figs.append((f"plot_quantiles_{key}_{gid}_",
+                         create_quantiles(f"GPU {gid}: {title}", [a * period for a in age], pct,
+                                          (q[:, 0], q[:, 1], q[:, 2]), mx, height)))
+    return figs
+
+
 def window_heatmap_figures(snap: NodeSnapshot, selected=None, height: int = 220) -> list | None:
     """[(key, Figure)]: per selected GPU the window heatmap (``rocmdash.ops.window_heatmap``)
     of every panel metric the snapshot's heatmap has - the metrics and the seconds of
@@ -284,7 +319,7 @@ def xcd_table(snap: NodeSnapshot, selected=None) -> dict | None:
 
 def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xcd: dict | None = None,
                   buckets: dict | None = None, trend: list | None = None, excursions: dict | None = None,
-                  heatmap: list | None = None, joint: list | None = None) -> None:
+                  heatmap: list | None = None, joint: list | None = None, quantiles: list | None = None) -> None:
     st.subheader("Average Metrics (Selected GPUs)")
     avg_cols = st.columns(4)
     for col, (key, spec) in zip(avg_cols, frame.avg_panels):
@@ -319,6 +354,12 @@ def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xc
         st.subheader("Window Trend (min / max band and mean per column of the window)")
         for i in range(0, len(trend), 4):
             for col, (key, fig) in zip(st.columns(4), trend[i : i + 4]):
+                with col:
+                    st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
+    if extended and quantiles:
+        st.subheader("Window Quantile Trend (exact percentiles per column of the window)")
+        for i in range(0, len(quantiles), 4):
+            for col, (key, fig) in zip(st.columns(4), quantiles[i : i + 4]):
                 with col:
                     st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
     if extended and heatmap:
@@ -411,7 +452,8 @@ def main(max_refreshes: int | None = None, data_source: str | None = None) -> No
                               window_trend_figures(snap, st.session_state.selected_gpus) if extended else None,
                               window_excursion_tables(snap, st.session_state.selected_gpus) if extended else None,
                               window_heatmap_figures(snap, st.session_state.selected_gpus) if extended else None,
-                              window_joint_figures(snap, st.session_state.selected_gpus) if extended else None)
+                              window_joint_figures(snap, st.session_state.selected_gpus) if extended else None,
+                              window_quantile_figures(snap, st.session_state.selected_gpus) if extended else None)
         n += 1
         if max_refreshes is not None and n >= max_refreshes:
             break

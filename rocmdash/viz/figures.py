@@ -440,6 +440,35 @@ def create_trend(title, age_s, lo, hi, mean, max_val=None, height=220) -> Figure
     return Figure(data, layout)
 
 
+QUANTILE_LINES = ("#27ae60", "#e67e22", "#c0392b")  # the lowest percentile to the highest
+
+
+def create_quantiles(title, age_s, pct, values, max_val=None, height=220) -> Figure:
+    """A window quantile trend (``rocmdash.ops.window_quantiles``) as three lines over the
+    trend's x axis (seconds before the newest sample, negative: time runs left to right).
+    ``age_s``: one entry per slot, oldest first; ``pct``: the three percentiles, naming the
+    traces (``p50``); ``values``: three sequences, one per percentile, an entry per slot. A
+    slot whose age or value is NaN (empty: no valid sample) is a null point - a gap, never a
+    line drawn across it. ``max_val``: the top of the y axis (None: autorange). No reference
+    counterpart."""
+    xs = [None if _num(a) is None else -_num(a) for a in age_s]
+    data = []
+    for p, ys, colour in zip(pct, values, QUANTILE_LINES):
+        y = [None if x is None or _num(v) is None else _num(v) for x, v in zip(xs, ys)]
+        data.append({"line": {"color": colour, "width": 2}, "mode": "lines", "name": f"p{float(p):g}", "x": list(xs),
+                     "y": y, "type": "scatter"})
+    yaxis = {"range": [0, _num(max_val)]} if max_val is not None and _num(max_val) else {}
+    layout = {
+        "title": {"text": title},
+        "xaxis": {"title": {"text": "seconds"}, "showgrid": True, "gridcolor": "lightgray"},
+        "yaxis": yaxis,
+        "margin": {"l": 40, "r": 20, "t": 40, "b": 40},
+        "height": _num(height),
+        "showlegend": True,
+    }
+    return Figure(data, layout)
+
+
 def create_heatmap(title, age_s, le, counts, height=220) -> Figure:
     """A window heatmap (``rocmdash.ops.window_heatmap``) as one Plotly ``heatmap`` trace:
     x = seconds before the newest sample (negative: time runs left to right), y = each bin's

@@ -129,6 +129,12 @@ class NodeSnapshot:
     window_joint: np.ndarray | None = None
     window_joint_pairs: tuple | None = None
     window_joint_bounds: np.ndarray | None = None
+    # Window quantile trend (rocmdash.ops.window_quantiles), when computed: per GPU
+    # [N, S, P + 1, 4] - the three percentiles window_quantiles_pct and their count of each of
+    # the trend's P + 1 column slots - and the slots' ages as for the trend
+    window_quantiles: np.ndarray | None = None
+    window_quantiles_age_rows: np.ndarray | None = None
+    window_quantiles_pct: tuple | None = None
 
     def __post_init__(self):
         self.values = np.asarray(self.values, dtype=np.float64)
