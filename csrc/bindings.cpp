@@ -14,6 +14,7 @@
 #include "publish.h"
 #include "rccl_comm.h"
 #include "long_window_buckets.h"
+#include "window_autocorr.h"
 #include "window_buckets.h"
 #include "window_excursions.h"
 #include "window_heatmap.h"
@@ -397,6 +398,20 @@ PYBIND11_MODULE(_native, m) {
           "Enqueue every series' window quantile trend after the last refresh: dst [S][columns + 1][4] floats "
           "(the three percentiles and the count per slot of window / columns rows).")
       .def(
+          "export_autocorr",
+          [](LongWindowSet& w, uint32_t span, uintptr_t scale, uint32_t L, uintptr_t dst, uintptr_t stream) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_autocorr(span, reinterpret_cast<const float*>(scale), L, reinterpret_cast<int64_t*>(dst),
+                                    reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_autocorr failed: " + std::to_string(e));
+          },
+          py::arg("span"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue every series' autocorrelation sums over the newest min(n, span) rows after the last refresh: scale "
+          "[S] floats -> dst [S][lags + 1][4] int64 (n, Sx, Sy, Sxy per lag).")
+      .def(
           "export_joint",
           [](LongWindowSet& w, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uintptr_t bounds, uint32_t B,
              uintptr_t dst, uintptr_t stream) {
@@ -601,6 +616,20 @@ PYBIND11_MODULE(_native, m) {
           py::arg("p2") = 99.0f,
           "Enqueue every series' window quantile trend after the last refresh: dst [S][columns + 1][4] floats "
           "(the three percentiles and the count per slot of window / columns rows).")
+      .def(
+          "export_autocorr",
+          [](const DeviceWindowSet& w, uint32_t span, uintptr_t scale, uint32_t L, uintptr_t dst, uintptr_t stream) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_autocorr(span, reinterpret_cast<const float*>(scale), L, reinterpret_cast<int64_t*>(dst),
+                                    reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_autocorr failed: " + std::to_string(e));
+          },
+          py::arg("span"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue every series' autocorrelation sums over the newest min(n, span) rows after the last refresh: scale "
+          "[S] floats -> dst [S][lags + 1][4] int64 (n, Sx, Sy, Sxy per lag).")
       .def(
           "export_joint",
           [](const DeviceWindowSet& w, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uintptr_t bounds, uint32_t B,
@@ -979,6 +1008,23 @@ PYBIND11_MODULE(_native, m) {
       py::arg("stream"),
       "Window heatmap of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) whose window is rows "
       "[head - n, head): bounds [cols][B] floats -> dst [cols][columns + 1][B + 1] int32 (per-bin counts per slot).");
+  m.def(
+      "autocorr_ring",
+      [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n, uint32_t span,
+         uintptr_t scale, uint32_t L, uintptr_t dst, uintptr_t stream) {
+        int e;
+        {
+          py::gil_scoped_release nogil;
+          e = launch_autocorr_ring(reinterpret_cast<const float*>(base), stride, cols, depth, head, n, span,
+                                   reinterpret_cast<const float*>(scale), L, reinterpret_cast<int64_t*>(dst),
+                                   reinterpret_cast<void*>(stream));
+        }
+        if (e != 0) throw std::runtime_error("autocorr_ring failed: " + std::to_string(e));
+      },
+      py::arg("base_ptr"), py::arg("stride"), py::arg("cols"), py::arg("depth"), py::arg("head"), py::arg("n"),
+      py::arg("span"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
+      "Autocorrelation sums of every column of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) over "
+      "the newest min(n, span) rows of the window [head - n, head): scale [cols] floats -> dst [cols][lags + 1][4] int64.");
   m.def(
       "joint_ring",
       [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n,

@@ -118,6 +118,13 @@ class DeviceWindowSet {
   // without a pair is not streamed. Returns a hipError_t (hipErrorInvalidValue before any
   // launch or write for a bad argument, a pair across rings included).
   int export_joint(const uint32_t* pairs, uint32_t K, const float* bounds, uint32_t B, int32_t* dst, void* stream) const;
+  // Enqueue, after the refresh that produced it, every series' window autocorrelation sums
+  // (window_autocorr.h, defined in window_autocorr.hip) over the newest min(n, span) rows of
+  // the window of the last refresh: scale device [num_series] floats, 1 <= L <= 1024, span a
+  // power of two in [2^6, 2^20]; dst device [num_series][L + 1][4] int64 = {n, Sx, Sy, Sxy}
+  // per lag, every word written (all zeroes before the first refresh and after invalidate()).
+  // Returns a hipError_t (hipErrorInvalidValue before any launch or write for a bad argument).
+  int export_autocorr(uint32_t span, const float* scale, uint32_t L, int64_t* dst, void* stream) const;
   // Enqueue, after the refresh that produced it, every series' window excursions
   // (window_excursions.h, defined in window_excursions.hip) over the window of the last
   // refresh: thresholds device [num_series][K], dst device [num_series][K][8] int32 (all

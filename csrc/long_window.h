@@ -269,6 +269,12 @@ class LongWindowSet {
   // device [K][B + 1][B + 1] int32, every cell written. A ring without a pair is not
   // streamed. Returns a hipError_t as export_buckets does.
   int export_joint(const uint32_t* pairs, uint32_t K, const float* bounds, uint32_t B, int32_t* dst, void* stream);
+  // Enqueue, after the refresh that left it on the device, every series' window
+  // autocorrelation sums (window_autocorr.h, defined in window_autocorr.hip) over the newest
+  // min(n, span) rows: scale device [num_series] floats, dst device [num_series][L + 1][4]
+  // int64 = {n, Sx, Sy, Sxy} per lag, every word written. Rows the host ring lost count as
+  // invalid. Returns a hipError_t as export_trend does.
+  int export_autocorr(uint32_t span, const float* scale, uint32_t L, int64_t* dst, void* stream);
   // Enqueue, after the refresh that left it on the device, every series' cumulative
   // le-buckets (long_window_buckets.h, defined in long_window_buckets.hip): bounds device
   // [num_series][B], dst device [num_series][B + 1] doubles, series in set order. One

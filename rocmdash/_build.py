@@ -38,6 +38,7 @@ SOURCES = [
     "window_heatmap.hip",
     "window_quantiles.hip",
     "window_joint.hip",
+    "window_autocorr.hip",
     "window_excursions.hip",
     "calib.hip",
     "publish.hip",

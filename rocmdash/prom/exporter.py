@@ -91,7 +91,8 @@ class LocalNodeSource(SnapshotSource):
 
     def __init__(self, devices=None, source: str = "auto", counters: str = "auto", cfg=None,
                  window_buckets: int | None = None, window_trend: int | None = None, window_excursions=None,
-                 replay=None, window_heatmap=None, window_joint=None, window_quantiles: int | None = None):
+                 replay=None, window_heatmap=None, window_joint=None, window_quantiles: int | None = None,
+                 window_autocorr=None):
         """``window_buckets`` = B > 0 (default: ``ROCMDASH_WINDOW_BUCKETS``, else off): also
         export every series' window as B cumulative le-buckets + ``+Inf``
         (``rocmdash_window_bucket``; GpuAgent.window_buckets) and their sum over the GPUs -
@@ -113,7 +114,11 @@ class LocalNodeSource(SnapshotSource):
         in ``/metrics``. ``window_quantiles`` = P > 0 (default: ``ROCMDASH_WINDOW_QUANTILES``,
         else off): the snapshot also carries every series' window as P + 1 columns of its three
         percentiles and their count (GpuAgent.window_quantiles), served as JSON by
-        ``GET /quantiles`` - never in ``/metrics``."""
+        ``GET /quantiles`` - never in ``/metrics``. ``window_autocorr`` = ``"L"`` or ``"L/SPAN"``
+        (``rocmdash.ops.window_autocorr.parse_autocorr``; default: ``ROCMDASH_WINDOW_AUTOCORR``, else
+        off): the snapshot also carries every series' autocorrelation sums
+        (GpuAgent.window_autocorr), served as JSON by ``GET /autocorr``, and ``/metrics`` gains
+        ``rocmdash_window_period_samples`` / ``_strength`` for the series that have a period."""
         from ..runtime import native
 
         if window_excursions is None:
@@ -150,6 +155,14 @@ class LocalNodeSource(SnapshotSource):
 
             self.heatmap = parse_heatmap(window_heatmap)
             check_columns(self.heatmap[0], (cfg or SamplerConfig()).window)
+        if window_autocorr is None:
+            window_autocorr = os.environ.get("ROCMDASH_WINDOW_AUTOCORR", "") or None
+        self.autocorr = None  # (L, span): rocmdash.ops.window_autocorr; GET /autocorr and the two period gauges
+        if window_autocorr is not None:  # checked before any agent starts its samplers
+            from ..config import SamplerConfig
+            from ..ops.window_autocorr import check_autocorr, parse_autocorr
+
+            self.autocorr = check_autocorr(*parse_autocorr(window_autocorr), (cfg or SamplerConfig()).window)
         if window_joint is None:
             window_joint = os.environ.get("ROCMDASH_WINDOW_JOINT", "") or None
         if window_joint is not None:  # the spec, its metrics and its rings: checked before any agent exists
@@ -200,6 +213,8 @@ class LocalNodeSource(SnapshotSource):
         self.heatmap_bounds = self.agents[0].default_bucket_bounds(self.heatmap[1]) if self.heatmap else None
         # and one set of joint bounds
         self.joint_bounds = self.agents[0].default_bucket_bounds(self.joint[1]) if self.joint else None
+        # and one autocorrelation scale
+        self.autocorr_scale = self.agents[0].default_autocorr_scale() if self.autocorr else None
 
     def collect(self):
         import torch
@@ -224,6 +239,9 @@ class LocalNodeSource(SnapshotSource):
             joint = None
             if self.joint is not None:
                 joint = [a.window_joint(self.joint[0], self.joint_bounds) for a in self.agents]
+            autocorr = None
+            if self.autocorr is not None:
+                autocorr = [a.window_autocorr(self.autocorr[0], self.autocorr[1], self.autocorr_scale) for a in self.agents]
             quantiles = quant_age = None
             if self.quantile_columns is not None:
                 quantiles = [a.window_quantiles(self.quantile_columns) for a in self.agents]
@@ -239,6 +257,8 @@ class LocalNodeSource(SnapshotSource):
                 heatmap = np.stack([h.to("cpu", non_blocking=False).numpy() for h in heatmap])
             if joint is not None:
                 joint = np.stack([j.to("cpu", non_blocking=False).numpy() for j in joint])
+            if autocorr is not None:
+                autocorr = np.stack([c.to("cpu", non_blocking=False).numpy() for c in autocorr])
             if quantiles is not None:
                 quantiles = np.stack([q.to("cpu", non_blocking=False).numpy() for q in quantiles])
             now_ns = time.time_ns()
@@ -278,6 +298,8 @@ class LocalNodeSource(SnapshotSource):
         if joint is not None:
             snap.window_joint, snap.window_joint_pairs = joint, tuple(self.joint[0])
             snap.window_joint_bounds = np.broadcast_to(self.joint_bounds, (len(ids),) + self.joint_bounds.shape)
+        if autocorr is not None:
+            snap.window_autocorr, snap.window_autocorr_span = autocorr, self.autocorr[1]
         if quantiles is not None:
             snap.window_quantiles, snap.window_quantiles_age_rows = quantiles, quant_age
             snap.window_quantiles_pct = tuple(self.agents[0].pct)
@@ -403,8 +425,33 @@ def render_joint(snap: NodeSnapshot) -> str | None:
     return json.dumps(doc, allow_nan=False)
 
 
+def render_autocorr(snap: NodeSnapshot) -> str | None:
+    """The snapshot's window autocorrelation as the ``/autocorr`` document, None when it carries
+    none: ``{"lags": L, "span": N, "series": [...], "gpus": {gpu_id: {metric: {"acf": [L + 1],
+    "pairs": [L + 1], "period_samples", "strength"}}}}``; ``pairs`` is ``n_k``, the pairs of valid
+    samples behind each lag; a lag without an acf and a series without a period are null."""
+    sums = getattr(snap, "window_autocorr", None)
+    if sums is None:
+        return None
+    from ..ops.window_autocorr import correlogram, pick_period
+
+    sums = np.asarray(sums)
+    series = list(snap.window_series)
+    gpus = {}
+    for g, gid in enumerate(snap.gpu_ids):
+        gpus[gid] = {}
+        for s, m in enumerate(series):
+            acf = correlogram(sums[g, s])
+            period, strength = pick_period(acf)
+            gpus[gid][m] = {"acf": _nullable(acf), "pairs": [int(v) for v in sums[g, s, :, 0]],
+                            "period_samples": period, "strength": strength}
+    span = getattr(snap, "window_autocorr_span", None)
+    doc = {"lags": int(sums.shape[2]) - 1, "span": int(span) if span is not None else None, "series": series, "gpus": gpus}
+    return json.dumps(doc, allow_nan=False)
+
+
 class Exporter:
-    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``, ``/heatmap``, ``/joint``, ``/quantiles``). With window buckets on,
+    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``, ``/heatmap``, ``/joint``, ``/quantiles``, ``/autocorr``). With window buckets on,
     ``rocmdash_window_bucket`` / ``rocmdash_node_window_bucket`` carry exact integer counts
     for any window the source keeps: up to 32768 samples from the resident sorted windows,
     longer windows (up to 2^26) streamed from the device rings and printed from float64."""
@@ -477,6 +524,17 @@ class Exporter:
             log.exception("collect failed")
             return None
 
+    def autocorr(self) -> str | None:
+        """The ``/autocorr`` document of a fresh collection; None when the source has no window
+        autocorrelation (the option is off) or the collection failed."""
+        try:
+            snap, _ = self.source.collect()
+            return render_autocorr(snap)
+        except Exception:
+            self.errors += 1
+            log.exception("collect failed")
+            return None
+
     def joint(self) -> str | None:
         """The ``/joint`` document of a fresh collection; None when the source has no window
         joint histogram (the option is off) or the collection failed."""
@@ -526,6 +584,12 @@ class Exporter:
                     doc = exporter.heatmap()
                     if doc is None:
                         body, ctype, code = b"no window heatmap (start with --window-heatmap PxB)\n", "text/plain", 404
+                    else:
+                        body, ctype, code = doc.encode(), "application/json", 200
+                elif self.path.split("?")[0] == "/autocorr":
+                    doc = exporter.autocorr()
+                    if doc is None:
+                        body, ctype, code = b"no window autocorrelation (start with --window-autocorr L[/SPAN])\n", "text/plain", 404
                     else:
                         body, ctype, code = doc.encode(), "application/json", 200
                 elif self.path.split("?")[0] == "/joint":
@@ -599,7 +663,18 @@ def main(argv=None) -> int:
     ap.add_argument("--window-quantiles", type=int, default=None, metavar="P",
                     help="also serve GET /quantiles: every series' window as P + 1 columns of its exact percentiles "
                          "and their count (a power of two in 8..1024; default ROCMDASH_WINDOW_QUANTILES, else off)")
+    ap.add_argument("--window-autocorr", default=None, metavar="L[/SPAN]",
+                    help="also serve GET /autocorr and the rocmdash_window_period_* gauges: every series' autocorrelation at "
+                         "lags 0..L (1..1024; 255, 511 and 1023 fill the kernel's blocks of 256 lags) over the newest SPAN rows of its window (a power of two in 64..1048576, "
+                         "default 65536) and its period (default ROCMDASH_WINDOW_AUTOCORR, else off)")
     args = ap.parse_args(argv)
+    if args.window_autocorr is not None:
+        from ..ops.window_autocorr import parse_autocorr
+
+        try:
+            parse_autocorr(args.window_autocorr)
+        except ValueError as e:
+            ap.error(f"--window-autocorr: {e}")
     if args.window_joint is not None:
         from ..models.schema import CTR_FIELDS, SMI_FIELDS
         from ..ops.window_joint import parse_joint
@@ -626,7 +701,8 @@ def main(argv=None) -> int:
     src = SyntheticSource(args.synthetic) if args.synthetic else LocalNodeSource(
         source=args.source, counters=args.counters, window_buckets=args.window_buckets, window_trend=args.window_trend,
         window_excursions=args.window_excursions, replay=args.replay, window_heatmap=args.window_heatmap,
-        window_joint=args.window_joint, window_quantiles=args.window_quantiles)
+        window_joint=args.window_joint, window_quantiles=args.window_quantiles,
+        window_autocorr=args.window_autocorr)
     exp = Exporter(src)
     exp.serve(args.host, args.port)
     log.info("serving /metrics on %s:%d", args.host, exp.port)

@@ -139,6 +139,7 @@ def render_snapshot(snap, hostname: str = "", extra_labels: dict | None = None, 
                         "Window statistic of a series over every GPU's window at once (node-wide)")
     render_window_buckets(exp, snap, hostname, extra)
     render_window_excursions(exp, snap, hostname, extra)
+    render_window_periods(exp, snap, hostname, extra)
     return exp.text()
 
 
@@ -208,6 +209,36 @@ def render_window_excursions(exp: Exposition, snap, hostname: str = "", extra: d
             for si, series in enumerate(snap.window_series):
                 for k in range(len(thr[si])):
                     exp.add(name, int(exc[g, si, k, field]), dict(base, metric=series, threshold=repr(float(thr[si][k]))), help_)
+
+
+def render_window_periods(exp: Exposition, snap, hostname: str = "", extra: dict | None = None) -> None:
+    """``rocmdash_window_period_samples`` and ``rocmdash_window_period_strength``, labelled
+    ``{gpu_id, metric}`` - and, like the excursion gauges, ``card_model``, ``hostname`` and the
+    exporter's extra labels - when the snapshot carries autocorrelation sums
+    (``NodeSnapshot.window_autocorr`` [N, S, L + 1, 4]) - only for the series that have a period
+    (``rocmdash.ops.window_autocorr.pick_period``). In samples, not seconds, as the excursions'
+    lengths are."""
+    sums = getattr(snap, "window_autocorr", None)
+    if sums is None or not len(snap.window_series):
+        return
+    from ..ops.window_autocorr import correlogram, pick_period
+
+    found = []
+    for g, gid in enumerate(snap.gpu_ids):
+        base = {"gpu_id": gid, "card_model": snap.card_models[g] or ""}
+        if hostname:
+            base["hostname"] = hostname
+        base.update(extra or {})
+        for si, series in enumerate(snap.window_series):
+            period, strength = pick_period(correlogram(sums[g][si]))
+            if period is not None:
+                found.append((dict(base, metric=series), period, strength))
+    for lab, period, _ in found:
+        exp.add("rocmdash_window_period_samples", int(period), lab,
+                "Period of a series over the newest rows of its window, in samples (absent: no period)")
+    for lab, _, strength in found:
+        exp.add("rocmdash_window_period_strength", strength, lab,
+                "Autocorrelation of a series at its period (at least 0.5; absent: no period)")
 
 
 def render_health(exp: Exposition, health, gpu_ids, hostname: str = "", extra: dict | None = None) -> None:

@@ -755,6 +755,53 @@ class GpuAgent:
             s += r.width
         return torch.from_numpy(out)
 
+    def default_autocorr_scale(self) -> np.ndarray:
+        """float32 ``[S]``: ``float32(4095 / axis)`` per series, the axis of
+        ``default_bucket_bounds`` (``rocmdash.ops.window_autocorr.default_scale``)."""
+        from ..ops.window_autocorr import default_scale
+
+        vram = self.smi_source.info().get("vram_total_mb")
+        return default_scale(self.series, self.info.power_limit_w, float(vram) if vram else None,
+                             card_model=self.info.card_model)
+
+    def window_autocorr(self, L, span=None, scale=None):
+        """Every series' autocorrelation sums, ``[S, L + 1, 4]`` int64: ``{n, Sx, Sy, Sxy}`` per
+        lag ``0 .. L`` over the newest ``min(n, span)`` rows of the window (``span`` default
+        65536), samples quantised by ``scale`` ([S] float32; default
+        ``default_autocorr_scale()``) - ``rocmdash.ops.window_autocorr`` states the semantics;
+        its ``correlogram`` and ``pick_period`` turn the integers into the acf and the period.
+        On a GPU the sums come from the device rings the last ``refresh()`` left there
+        (csrc/window_autocorr.hip), short or long windows alike, in stream order; the scale is
+        uploaded once per scale object and the output is reused by the next call with the same
+        lags and the same scale object."""
+        import torch
+
+        from ..ops.window_autocorr import check_autocorr, check_scale, window_autocorr_reference
+
+        L, span = check_autocorr(L, span, self.window)
+        if scale is None:
+            scale = getattr(self, "_default_autocorr_scale", None)
+            if scale is None:
+                scale = self._default_autocorr_scale = self.default_autocorr_scale()
+        S = len(self.series)
+        if self.dws is not None:
+            cached = getattr(self, "_autocorr", None)
+            if cached is None or cached[0] != L or cached[1] is not scale:
+                dev = cached[2] if cached is not None and cached[1] is scale else torch.from_numpy(check_scale(scale, S)).to(self.device)
+                out = torch.empty((S, L + 1, 4), dtype=torch.int64, device=self.device)
+                cached = self._autocorr = (L, scale, dev, out)
+            _, _, dev, out = cached
+            self.dws.export_autocorr(span, dev.data_ptr(), L, out.data_ptr(), _current_raw_stream(self.device_index))
+            return out
+        sc = check_scale(scale, S)
+        out, s = np.zeros((S, L + 1, 4), dtype=np.int64), 0
+        for r in self.rings:
+            rows, _ = r.window(self.window)
+            rows = np.asarray(rows, dtype=np.float32).reshape(-1, r.width)
+            out[s : s + r.width] = window_autocorr_reference(rows, sc[s : s + r.width], L, span)
+            s += r.width
+        return torch.from_numpy(out)
+
     def default_excursion_thresholds(self, fractions=(0.5, 0.75, 0.9)) -> np.ndarray:
         """``[S, K]`` float32 thresholds of this GPU's series: ``fractions`` of each series'
         axis, the axis of ``default_bucket_bounds``

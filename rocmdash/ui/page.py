@@ -214,6 +214,37 @@ def window_quantile_figures(snap: NodeSnapshot, selected=None, height: int = 220
     return figs
 
 
+def window_autocorr_figures(snap: NodeSnapshot, selected=None, height: int = 220) -> list | None:
+    """[(key, Figure)]: per selected GPU the correlogram (``rocmdash.ops.window_autocorr``) of
+    every panel metric the snapshot's autocorrelation has - the metrics of
+    ``window_trend_figures`` - as a line over the lag with a marker at the period (None if the
+    snapshot carries none)."""
+    sums = getattr(snap, "window_autocorr", None)
+    if sums is None:
+        return None
+    from ..ops.window_autocorr import correlogram, pick_period
+    from ..viz.figures import create_autocorr
+    from ..viz.panels import EXTENDED_PANELS, POWER, TEMP, UTIL
+
+    index = {s: i for i, s in enumerate(snap.window_series)}
+    sel = set(str(g) for g in selected) if selected is not None else None
+    figs = []
+    for g, gid in enumerate(snap.gpu_ids):
+        if sel is not None and gid not in sel:
+            continue
+        panels = [(UTIL, "GPU Utilization (%)", "gpu_util", 100.0), (TEMP, "Temperature (°C)", "temp", 100.0),
+                  (POWER, "Power Usage (W)", "power", snap.power_max(gid))] + list(EXTENDED_PANELS)
+        for col, title, key, _ in panels:
+            s = index.get(col)
+            if s is None:
+                continue
+            acf = correlogram(sums[g][s])
+            period, _ = pick_period(acf)
+            figs.append((f"plot_autocorr_{key}_{gid}_",
+                         create_autocorr(f"GPU {gid}: {title}", acf, [title], [period], height)))
+    return figs
+
+
 def window_heatmap_figures(snap: NodeSnapshot, selected=None, height: int = 220) -> list | None:
     """[(key, Figure)]: per selected GPU the window heatmap (``rocmdash.ops.window_heatmap``)
     of every panel metric the snapshot's heatmap has - the metrics and the seconds of
@@ -319,7 +350,8 @@ def xcd_table(snap: NodeSnapshot, selected=None) -> dict | None:
 
 def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xcd: dict | None = None,
                   buckets: dict | None = None, trend: list | None = None, excursions: dict | None = None,
-                  heatmap: list | None = None, joint: list | None = None, quantiles: list | None = None) -> None:
+                  heatmap: list | None = None, joint: list | None = None, quantiles: list | None = None,
+                  autocorr: list | None = None) -> None:
     st.subheader("Average Metrics (Selected GPUs)")
     avg_cols = st.columns(4)
     for col, (key, spec) in zip(avg_cols, frame.avg_panels):
@@ -360,6 +392,12 @@ def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xc
         st.subheader("Window Quantile Trend (exact percentiles per column of the window)")
         for i in range(0, len(quantiles), 4):
             for col, (key, fig) in zip(st.columns(4), quantiles[i : i + 4]):
+                with col:
+                    st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
+    if extended and autocorr:
+        st.subheader("Window Autocorrelation (acf over the lag in samples; the marker is the period)")
+        for i in range(0, len(autocorr), 4):
+            for col, (key, fig) in zip(st.columns(4), autocorr[i : i + 4]):
                 with col:
                     st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
     if extended and heatmap:
@@ -453,7 +491,8 @@ def main(max_refreshes: int | None = None, data_source: str | None = None) -> No
                               window_excursion_tables(snap, st.session_state.selected_gpus) if extended else None,
                               window_heatmap_figures(snap, st.session_state.selected_gpus) if extended else None,
                               window_joint_figures(snap, st.session_state.selected_gpus) if extended else None,
-                              window_quantile_figures(snap, st.session_state.selected_gpus) if extended else None)
+                              window_quantile_figures(snap, st.session_state.selected_gpus) if extended else None,
+                              window_autocorr_figures(snap, st.session_state.selected_gpus) if extended else None)
         n += 1
         if max_refreshes is not None and n >= max_refreshes:
             break

@@ -505,6 +505,33 @@ def create_heatmap(title, age_s, le, counts, height=220) -> Figure:
     return Figure([trace], layout)
 
 
+def create_autocorr(title, acf, names=None, periods=None, height=220) -> Figure:
+    """A window correlogram (``rocmdash.ops.window_autocorr``) as one Plotly ``scatter`` line per
+    series over the lag in samples, with a marker at each series' period. ``acf``: ``[L + 1]`` or
+    ``[K][L + 1]`` (NaN: a lag without an acf, drawn as a gap); ``names``: the K trace names;
+    ``periods``: per series its period in samples or None. No reference counterpart."""
+    rows = [list(r) for r in acf] if len(acf) and hasattr(acf[0], "__len__") else [list(acf)]
+    names = list(names) if names is not None else [f"series {k}" for k in range(len(rows))]
+    periods = list(periods) if periods is not None else [None] * len(rows)
+    traces = []
+    for k, row in enumerate(rows):
+        y = [None if v is None or v != v else _num(v) for v in row]
+        traces.append({"mode": "lines", "name": names[k], "x": list(range(len(y))), "y": y, "type": "scatter"})
+        p = periods[k]
+        if p is not None and 0 <= int(p) < len(y) and y[int(p)] is not None:
+            traces.append({"marker": {"size": 9, "symbol": "diamond"}, "mode": "markers", "name": f"{names[k]} period {int(p)}",
+                           "x": [int(p)], "y": [y[int(p)]], "type": "scatter"})
+    layout = {
+        "title": {"text": title},
+        "xaxis": {"title": {"text": "lag (samples)"}},
+        "yaxis": {"range": [-1, 1], "title": {"text": "acf"}},
+        "margin": {"l": 40, "r": 20, "t": 40, "b": 40},
+        "height": _num(height),
+        "showlegend": len(rows) > 1,
+    }
+    return Figure(traces, layout)
+
+
 def create_joint(title, le_x, le_y, counts, x_title=None, y_title=None, height=260) -> Figure:
     """A window joint histogram (``rocmdash.ops.window_joint``) as one Plotly ``heatmap`` trace:
     x = each bin's upper bound of the pair's first series, y = of its second, z = the rows in

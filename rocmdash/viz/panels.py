@@ -129,6 +129,10 @@ class NodeSnapshot:
     window_joint: np.ndarray | None = None
     window_joint_pairs: tuple | None = None
     window_joint_bounds: np.ndarray | None = None
+    # Window autocorrelation sums (rocmdash.ops.window_autocorr), when computed: per GPU
+    # [N, S, L + 1, 4] int64 = {n, Sx, Sy, Sxy} per lag, and the span they were taken over
+    window_autocorr: np.ndarray | None = None
+    window_autocorr_span: int | None = None
     # Window quantile trend (rocmdash.ops.window_quantiles), when computed: per GPU
     # [N, S, P + 1, 4] - the three percentiles window_quantiles_pct and their count of each of
     # the trend's P + 1 column slots - and the slots' ages as for the trend
