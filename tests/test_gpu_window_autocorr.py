@@ -12,6 +12,8 @@ import os
 import numpy as np
 import pytest
 
+from _window_exports import _assert_autocorr as _check
+
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,21 +38,6 @@ def _rows(seed, S, n, nan=0.0):
 
 def _scale(S):
     return np.full(S, np.float32(4095.0 / AXIS), np.float32)
-
-
-def _check(got, x, scale, L, span=None, what=""):
-    """``got`` [S, L + 1, 4] against the reference over ``x`` [S, n]."""
-    from rocmdash.ops.window_autocorr import window_autocorr_reference
-
-    got = np.asarray(got)
-    want = window_autocorr_reference(x.T, scale, L, span)
-    assert got.dtype == np.int64 and got.shape == want.shape, (got.shape, got.dtype, want.shape)
-    if not np.array_equal(got, want):
-        s, k, j = (int(v[0]) for v in np.nonzero(got != want))
-        raise AssertionError(f"{what} n {x.shape[1]} L {L}: {np.count_nonzero(got != want)} words differ, first series {s} "
-                             f"lag {k} word {j}: {got[s, k, j]} != {want[s, k, j]}")
-    assert (want[:, 0, 1] == want[:, 0, 2]).all()
-    return want
 
 
 def _run(cuda, x, L, span=None, head=None, window=None):

@@ -12,6 +12,7 @@ import pytest
 import _exact
 from _bucket_bounds import bounds_row as _bounds_row
 from _bucket_bounds import one_shot_rows as _one_shot_rows
+from _window_exports import _assert_counts
 
 pytestmark = pytest.mark.gpu
 
@@ -21,17 +22,6 @@ KINDS = ("on_samples", "between")
 def _bounds(x, B, kinds):
     """[S, B] for ``x`` [S, n]; series s takes kinds[s % len(kinds)]."""
     return np.stack([_bounds_row(x[s][~np.isnan(x[s])], B, kinds[s % len(kinds)]) for s in range(len(x))])
-
-
-def _assert_counts(got, x, bounds, what=""):
-    from rocmdash.ops.window_buckets import window_buckets_reference
-
-    got = np.asarray(got)
-    assert got.dtype == np.float32
-    want = window_buckets_reference(x, bounds)
-    np.testing.assert_array_equal(got.astype(np.int64), want, err_msg=what)
-    np.testing.assert_array_equal(got, want.astype(np.float32), err_msg=what)  # whole numbers, nothing else
-    return want
 
 
 @pytest.mark.parametrize("kind", KINDS)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import _exact
+from _window_exports import _assert_heatmap
 
 pytestmark = pytest.mark.gpu
 
@@ -42,21 +43,6 @@ def _quantile_bounds(x, B):
         if len(u) >= B:
             out[s] = u[np.round(np.linspace(0, len(u) - 1, B)).astype(np.int64)]
     return out
-
-
-def _assert_heatmap(got, rows, head, W, P, bounds, what=""):
-    """``got`` [S, P + 1, B + 1] against the reference over ``rows`` [n, S] = rows head - n .. head - 1."""
-    from rocmdash.ops.window_heatmap import window_heatmap_reference
-
-    got = np.asarray(got)
-    want = window_heatmap_reference(rows, head, W, P, bounds)
-    assert got.dtype == np.int32 and got.shape == want.shape, (got.shape, got.dtype, want.shape)
-    if not np.array_equal(got, want):
-        s, j, k = (int(v[0]) for v in np.nonzero(got != want))
-        raise AssertionError(f"{what} head {head} n {len(rows)} W {W} P {P} B {bounds.shape[1]}: "
-                             f"{np.count_nonzero(got != want)} counts differ, first series {s} slot {j} bin {k}: "
-                             f"{got[s, j, k]} != {want[s, j, k]}; slot: {got[s, j]} != {want[s, j]}")
-    return want
 
 
 _ROWS = {}

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import _exact
+from _window_exports import _assert_joint
 
 pytestmark = pytest.mark.gpu
 
@@ -46,25 +47,6 @@ def _quantile_bounds(x, B):
         if len(u) >= B:
             out[s] = u[np.round(np.linspace(0, len(u) - 1, B)).astype(np.int64)]
     return out
-
-
-def _assert_joint(got, rows, pairs, bounds, what=""):
-    """``got`` [K, B + 1, B + 1] against the reference over ``rows`` [n, S]; the cells of a pair
-    sum to the rows valid in both series."""
-    from rocmdash.ops.window_joint import window_joint_reference
-
-    got = np.asarray(got)
-    want = window_joint_reference(rows, pairs, bounds)
-    assert got.dtype == np.int32 and got.shape == want.shape, (got.shape, got.dtype, want.shape)
-    if not np.array_equal(got, want):
-        k, i, j = (int(v[0]) for v in np.nonzero(got != want))
-        raise AssertionError(f"{what} n {len(rows)} B {bounds.shape[1]} pairs {pairs}: "
-                             f"{np.count_nonzero(got != want)} cells differ, first pair {k} = {pairs[k]} cell ({i}, {j}): "
-                             f"{got[k, i, j]} != {want[k, i, j]}; sums {got[k].sum()} != {want[k].sum()}")
-    rows = np.asarray(rows)
-    for k, (a, b) in enumerate(pairs):
-        assert want[k].sum() == np.count_nonzero(~np.isnan(rows[:, a]) & ~np.isnan(rows[:, b]))
-    return want
 
 
 _ROWS = {}

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import _exact
+from _window_exports import _assert_quantiles
 from test_gpu_window_trend import SHAPES, _Rings, _SLICES, _assert_all_empty, _bits, _one_shot_rows
 
 pytestmark = pytest.mark.gpu
@@ -28,47 +29,6 @@ def _nonfinite_in(sl):
     """Local indices, within the slice ``sl`` of _one_shot_rows, of the series with infinities."""
     idx = list(range(*sl.indices(len(_exact.FAMILIES) + 2)))
     return tuple(idx.index(g) for g in _NONFINITE if g in idx)
-
-
-def _assert_quantiles(got, rows, head, W, P, pct, nonfinite_ok=(), what=""):
-    """``got`` [S, P + 1, 4] against the oracle over ``rows`` [n, S] = rows head - n .. head - 1.
-    Returns the number of (series, slot, percentile) comparisons made; a comparison is left
-    out only for a series in ``nonfinite_ok`` interpolating against an infinite order statistic."""
-    from rocmdash.ops.window_trend import trend_geometry
-
-    got = np.asarray(got)
-    n, S = rows.shape
-    assert got.dtype == np.float32 and got.shape == (S, P + 1, 4), (got.shape, got.dtype)
-    _, ranges = trend_geometry(head, n, W, P)
-    first, made = head - n, 0
-    for j, (b, e) in enumerate(ranges):
-        g = got[:, j]
-        where = f"{what} slot {j} rows [{b}, {e}) head {head} n {n} W {W} P {P}"
-        if e <= b:
-            assert (g[:, 3] == 0).all() and np.isnan(g[:, :3]).all(), f"{where}: not empty: {g}"
-            continue
-        ex = _exact.exact_stats(np.ascontiguousarray(rows[b - first:e - first]), pct)
-        np.testing.assert_array_equal(g[:, 3], ex.count.astype(np.float32), err_msg=f"{where}: count")
-        for s in range(S):
-            for q in range(3):
-                have = g[s, q]
-                if not ex.nv[s]:
-                    assert np.isnan(have), f"{where} series {s}: {g[s]} with no valid sample"
-                    made += 1
-                    continue
-                x0, x1, f, want = ex.x0[s, q], ex.x1[s, q], ex.frac[s, q], ex.percentile[s, q]
-                msg = (f"{where} series {s}: p{ex.pct[q]:g} = {have!r}, oracle {want!r} (x0 {x0!r} at "
-                       f"{ex.pos[s, 2 * q]}, x1 {x1!r} at {ex.pos[s, 2 * q + 1]}, frac {f!r}, nv {ex.nv[s]})")
-                if f == 0 or x0 == x1:
-                    assert _exact._same(have, x0), msg
-                elif not (np.isfinite(x0) and np.isfinite(x1)):
-                    assert s in nonfinite_ok, msg + ": an infinite order statistic in a finite series"
-                    continue
-                else:
-                    assert _exact._within_one_ulp(have, want), msg
-                    assert x0 <= have <= x1, msg + ": outside [x0, x1]"
-                made += 1
-    return made
 
 
 def _slots(head, n, c):

@@ -12,46 +12,11 @@ import numpy as np
 import pytest
 
 import _exact
+from _window_exports import _assert_trend, _bits
 
 pytestmark = pytest.mark.gpu
 
 PCT = (50.0, 90.0, 99.0)  # exact_stats wants percentiles; the trend has none
-
-
-def _bits(x):
-    return np.ascontiguousarray(x, np.float32).view(np.uint32)
-
-
-def _assert_trend(got, rows, head, W, P, what=""):
-    """``got`` [S, P + 1, 4] against the oracle over ``rows`` [n, S] = rows head - n .. head - 1.
-    Returns the number of non-empty slots."""
-    from rocmdash.ops.window_trend import trend_geometry
-
-    got = np.asarray(got)
-    n, S = rows.shape
-    assert got.dtype == np.float32 and got.shape == (S, P + 1, 4), (got.shape, got.dtype)
-    _, ranges = trend_geometry(head, n, W, P)
-    first, full = head - n, 0
-    for j, (b, e) in enumerate(ranges):
-        g = got[:, j]
-        where = f"{what} slot {j} rows [{b}, {e}) head {head} n {n} W {W} P {P}"
-        if e <= b:
-            assert (g[:, 3] == 0).all() and np.isnan(g[:, :3]).all(), f"{where}: not empty: {g}"
-            continue
-        full += 1
-        ex = _exact.exact_stats(np.ascontiguousarray(rows[b - first:e - first]), PCT)
-        np.testing.assert_array_equal(g[:, 3], ex.count.astype(np.float32), err_msg=f"{where}: count")
-        for s in range(S):
-            if not ex.nv[s]:
-                assert np.isnan(g[s, :3]).all(), f"{where} series {s}: {g[s]} with no valid sample"
-                continue
-            assert _bits(g[s, 0]) == _bits(ex.min[s]), f"{where} series {s}: min {g[s, 0]!r} != {ex.min[s]!r}"
-            assert _bits(g[s, 1]) == _bits(ex.max[s]), f"{where} series {s}: max {g[s, 1]!r} != {ex.max[s]!r}"
-            if not (np.isfinite(ex.mean[s]) and np.isfinite(ex.mean_abs[s])):
-                continue
-            err, bound = abs(float(g[s, 2]) - float(ex.mean[s])), _exact.mean_bound(ex, s, sum_group=1)
-            assert err <= bound, f"{where} series {s}: mean {g[s, 2]!r} vs {ex.mean[s]!r}: |diff| {err:.3e} > {bound:.3e}"
-    return full
 
 
 _ROWS = {}
