@@ -1,5 +1,7 @@
-"""Bounds and samples that make the streaming le-bucket kernel (csrc/long_window_buckets.hip)
-WALK: a lane that left its bin guesses the new one as if its bounds were evenly spaced,
+"""Bounds and samples that make the kernels that bin by the le rule WALK. Three kernels hold a
+private copy of it - the streaming le-bucket kernel (csrc/long_window_buckets.hip), the window
+heatmap (csrc/window_heatmap.hip) and the joint histogram (csrc/window_joint.hip): a lane that
+left its bin guesses the new one as if its bounds were evenly spaced,
 
     g = clamp(ceil((x - b[0]) * (B - 1) / (b[B-1] - b[0])), 0, B)        (NaN -> 0)
 
@@ -8,7 +10,13 @@ walk is at most one step; the families here are finite, strictly ascending and u
 that the guess is far off - below, above, or no guess at all (the span overflows, the inverse
 is inf) - and the walk is what the counts depend on. ``guess_distance`` is a model of the
 guess alone, for preconditions ("these inputs need the walk"); it is never an expected value:
-those come from ``rocmdash.ops.window_buckets``' references.
+those come from the references of ``rocmdash.ops.window_buckets``, ``window_heatmap`` and
+``window_joint``.
+
+What the three kernels' tests share is here too: the launch schedule after which every bounds
+family has met every sample family (``_shifts``), the windows of a ring (``_windows``), a
+ring's columns (``_ring_inputs``), the walk precondition over a window's own samples
+(``_walkers``) and NaN put into a column after its bounds were derived (``with_nans``).
 
 Also the bounds the sorted-window tests use (``bounds_row``: on samples / one ulp beside
 them) and their input rows (``one_shot_rows``). Plain numpy, no GPU and no native code;
@@ -202,6 +210,150 @@ def column(rng, bounds_name: str, sample_kind: str, j: int, n: int, B: int) -> t
     b = bounds_for(bounds_name, B, v)
     x = v if sample_kind == "exact" else SAMPLES[sample_kind](rng, n, b)
     return b, np.ascontiguousarray(x, F32)
+
+
+# ---- rings: what the tests of the three kernels launch ---------------------------------------
+F, NS = len(BOUNDS), len(SAMPLE_KINDS)
+UNREAD = np.float32(1.0)  # what the columns >= cols hold: a bound of ulp_run and clustered, a count for any
+
+
+def _shifts(cols):
+    """(offset, shift): column c takes bounds family (c + offset) % F and sample family
+    (c + shift) % NS. The fewest launches, in order, after which every bounds family has met
+    every sample family in some column."""
+    seen, keep = set(), []
+    for o in range(F):
+        for s in range(NS):
+            pairs = {((c + o) % F, (c + s) % NS) for c in range(cols)}
+            if not pairs <= seen:
+                seen |= pairs
+                keep.append((o, s))
+    assert len(seen) == F * NS
+    return keep
+
+
+def _windows(depth):
+    """(kind, head, n): one row; part-filled, unwrapped; the full ring as two blocks; a
+    part-filled window that wraps, at a head past 2^32."""
+    part = depth // 2 + 3
+    w = [("n = 1", depth + 7, 1), ("part, unwrapped", part, part), ("full, two blocks", 2 * depth + depth // 3 + 1, depth),
+         ("wrapped, head > 2^32", (1 << 32) + 12345, part)]
+    first = [(head - n) & (depth - 1) for _, head, n in w]
+    assert first[1] == 0 and first[2] > 0 and first[3] + part > depth and w[3][1] - part > 1 << 32
+    return w
+
+
+def _ring_inputs(depth, stride, cols, B, o, s):
+    """(rows [depth, stride], bounds [cols, B], names per column): every row holds samples (a
+    window that is not full leaves rows that would count outside it)."""
+    rng = np.random.default_rng(1000 * depth + 100 * stride + 10 * B + 7 * o + s)
+    rows = np.full((depth, stride), UNREAD, np.float32)
+    bounds = np.empty((cols, B), np.float32)
+    names = []
+    for c in range(cols):
+        names.append((BOUNDS[(c + o) % F], SAMPLE_KINDS[(c + s) % NS]))
+        bounds[c], rows[:, c] = column(rng, names[c][0], names[c][1], c + o, depth, B)
+    return rows, bounds, names
+
+
+def _walkers(rows, bounds, names, head, n):
+    """The walking families among the columns whose samples visit every bin, each held to its
+    precondition over the window's own samples."""
+    depth = rows.shape[0]
+    slots = np.arange(head - n, head, dtype=np.int64) & (depth - 1)
+    found = set()
+    for c, (family, kind) in enumerate(names):
+        if family in WALKS and kind in VISIT_EVERY_BIN:
+            x = rows[slots, c]
+            assert walks_enough(family, x, bounds[c]), (c, family, kind, walk_reached(x, bounds[c]))
+            found.add(family)
+    return found
+
+
+def with_nans(rng, x, share) -> np.ndarray:
+    """A copy of the column ``x`` with about ``share`` of its samples replaced by NaN - after the
+    column's bounds were derived, so they stay what they were. NaN only removes samples: a walk
+    precondition is computed on the column before this."""
+    x = np.array(x, F32)
+    x[rng.random(len(x)) < share] = np.nan
+    return x
+
+
+# The rings of the heatmap's and the joint histogram's one-shot tests (test_gpu_window_heatmap_bounds.py,
+# test_gpu_window_joint_bounds.py; test_bucket_bounds_walks.py holds their inputs to the walk
+# preconditions without a GPU). Heatmap: (depth, stride, cols, P, rows_per_col), the window P x
+# rows_per_col = depth; one wave streams a slot of stride x rows_per_col <= 2048 floats, eight waves a larger one.
+HEATMAP_RINGS = [(1024, 1, 1, 8, 128), (1024, 3, 3, 8, 128), (1024, 12, 7, 8, 128), (1024, 13, 13, 64, 16),
+                 (1024, 23, 23, 8, 128), (4096, 64, 64, 8, 512)]
+HEATMAP_B = [1, 2, 3, 16, 63]
+JOINT_RINGS = [(1024, 2, 2), (1024, 5, 5), (1024, 7, 7), (1024, 12, 7), (1024, 23, 23), (4096, 64, 64)]
+JOINT_B = [1, 2, 3, 16, 31]
+NAN_SHARE = 0.05
+
+
+def _launch_inputs(depth, stride, cols, B, i, o, s):
+    """Launch ``i`` of a ring's schedule ``_shifts(cols)[i] == (o, s)``: (the rows of
+    ``_ring_inputs``, the rows the kernel gets, bounds, names). In every second launch the
+    kernel's rows have NaN in NAN_SHARE of every column that is not ``exact`` (those hold the
+    NaN of their own families)."""
+    clean, bounds, names = _ring_inputs(depth, stride, cols, B, o, s)
+    rows = clean.copy()
+    if i % 2:
+        rng = np.random.default_rng(31 * depth + 17 * stride + 5 * B + i)
+        for c, (_, kind) in enumerate(names):
+            if kind != "exact":
+                rows[:, c] = with_nans(rng, clean[:, c], NAN_SHARE)
+    return clean, rows, bounds, names
+
+
+# ---- window sets: what the export tests of the heatmap and the joint histogram refresh -----------
+EXPORT_KINDS = ("on_samples", "between", "geometric", "huge_span")  # by series, as the long buckets' export test
+EXPORT_WIDTHS = (8, 13)  # LongWindowSet: two segments, unaligned rows
+
+
+def export_steps(W):
+    """Rows pushed before each refresh: a part-filled window, a full one, +1 row, none, +100,
+    +257 and enough to wrap the device ring (W rows of a LongWindowSet, 2 W of a DeviceWindowSet)."""
+    return [W // 2 + 5, W // 2 + 32, 1, 0, 100, 257, W + W // 4 + 7]
+
+
+class ExportRings:
+    """Two rings of 8 and 13 series fed the 21 ``_exact`` families, in a LongWindowSet
+    (``long``) or a DeviceWindowSet of window W, with everything pushed kept oldest first."""
+
+    def __init__(self, nat, W, long, seed):
+        nat.set_pinned_host_rings(True)
+        if not long:
+            nat.set_pull_mode(True)
+        self.W, self.S = W, sum(EXPORT_WIDTHS)
+        self.rings = [nat.SeriesRing(w, 2 * W if long else 8 * W) for w in EXPORT_WIDTHS]
+        self.ws = nat.LongWindowSet(W, 0) if long else nat.DeviceWindowSet(W, 0)
+        for r in self.rings:
+            self.ws.add_ring(r)
+        self.rows = np.zeros((0, self.S), F32)
+        self.rng = np.random.default_rng(seed)
+        self.t = 0
+
+    def push(self, k):
+        if not k:
+            return
+        x = _exact.family_rows(self.rng, self.t, k, self.W, width=self.S, blips=(5, self.W + 8))
+        ts = np.arange(self.t + 1, self.t + 1 + k, dtype=np.uint64)
+        c0 = 0
+        for r, w in zip(self.rings, EXPORT_WIDTHS):
+            r.push_many(np.ascontiguousarray(x[:, c0:c0 + w]), ts)
+            c0 += w
+        self.rows = np.concatenate([self.rows, x])
+        self.t += k
+
+    def window(self):
+        """[n, S]: the rows the set holds after a refresh, oldest first (head = ``t``)."""
+        return self.rows[-self.W:]
+
+    def bounds(self, B):
+        """[S, B]: EXPORT_KINDS by series, the two from-samples kinds from this very window."""
+        x = self.window()
+        return np.stack([bounds_for(EXPORT_KINDS[s % len(EXPORT_KINDS)], B, x[:, s]) for s in range(self.S)])
 
 
 _ROWS = {}

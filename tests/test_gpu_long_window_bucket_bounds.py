@@ -16,69 +16,16 @@ import pytest
 
 import _bucket_bounds as bb
 import _exact
+from _bucket_bounds import _ring_inputs, _shifts, _walkers, _windows
 
 pytestmark = pytest.mark.gpu
 
 COUNT = 7  # the window statistics' count column
-F, NS = len(bb.BOUNDS), len(bb.SAMPLE_KINDS)
-UNREAD = np.float32(1.0)  # what the columns >= cols hold: a bound of ulp_run and clustered, a count for any
+F = len(bb.BOUNDS)
 
 
 def _report(request, compared):
     print(f"[buckets] {request.node.name}: {compared} count comparisons")
-
-
-def _shifts(cols):
-    """(offset, shift): column c takes bounds family (c + offset) % F and sample family
-    (c + shift) % NS. The fewest launches, in order, after which every bounds family has met
-    every sample family in some column."""
-    seen, keep = set(), []
-    for o in range(F):
-        for s in range(NS):
-            pairs = {((c + o) % F, (c + s) % NS) for c in range(cols)}
-            if not pairs <= seen:
-                seen |= pairs
-                keep.append((o, s))
-    assert len(seen) == F * NS
-    return keep
-
-
-def _windows(depth):
-    """(kind, head, n): one row; part-filled, unwrapped; the full ring as two blocks; a
-    part-filled window that wraps, at a head past 2^32."""
-    part = depth // 2 + 3
-    w = [("n = 1", depth + 7, 1), ("part, unwrapped", part, part), ("full, two blocks", 2 * depth + depth // 3 + 1, depth),
-         ("wrapped, head > 2^32", (1 << 32) + 12345, part)]
-    first = [(head - n) & (depth - 1) for _, head, n in w]
-    assert first[1] == 0 and first[2] > 0 and first[3] + part > depth and w[3][1] - part > 1 << 32
-    return w
-
-
-def _ring_inputs(depth, stride, cols, B, o, s):
-    """(rows [depth, stride], bounds [cols, B], names per column): every row holds samples (a
-    window that is not full leaves rows that would count outside it)."""
-    rng = np.random.default_rng(1000 * depth + 100 * stride + 10 * B + 7 * o + s)
-    rows = np.full((depth, stride), UNREAD, np.float32)
-    bounds = np.empty((cols, B), np.float32)
-    names = []
-    for c in range(cols):
-        names.append((bb.BOUNDS[(c + o) % F], bb.SAMPLE_KINDS[(c + s) % NS]))
-        bounds[c], rows[:, c] = bb.column(rng, names[c][0], names[c][1], c + o, depth, B)
-    return rows, bounds, names
-
-
-def _walkers(rows, bounds, names, head, n):
-    """The walking families among the columns whose samples visit every bin, each held to its
-    precondition over the window's own samples."""
-    depth = rows.shape[0]
-    slots = np.arange(head - n, head, dtype=np.int64) & (depth - 1)
-    found = set()
-    for c, (family, kind) in enumerate(names):
-        if family in bb.WALKS and kind in bb.VISIT_EVERY_BIN:
-            x = rows[slots, c]
-            assert bb.walks_enough(family, x, bounds[c]), (c, family, kind, bb.walk_reached(x, bounds[c]))
-            found.add(family)
-    return found
 
 
 RINGS = [(1024, 1, 1), (1024, 3, 3), (1024, 12, 7), (1024, 13, 13), (4096, 64, 64)]
