@@ -21,6 +21,7 @@
 #include "window_joint.h"
 #include "window_quantiles.h"
 #include "window_trend.h"
+#include "window_xcorr.h"
 
 namespace rocmdash {
 int launch_spin(uint32_t workgroups, double us, void* stream);  // calib.hip
@@ -412,6 +413,26 @@ PYBIND11_MODULE(_native, m) {
           "Enqueue every series' autocorrelation sums over the newest min(n, span) rows after the last refresh: scale "
           "[S] floats -> dst [S][lags + 1][4] int64 (n, Sx, Sy, Sxy per lag).")
       .def(
+          "export_xcorr",
+          [](LongWindowSet& w, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uint32_t span, uintptr_t scale,
+             uint32_t L, uintptr_t dst, uintptr_t stream) {
+            std::vector<uint32_t> flat;
+            for (const auto& p : pairs) {
+              flat.push_back(p.first);
+              flat.push_back(p.second);
+            }
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_xcorr(flat.data(), uint32_t(pairs.size()), span, reinterpret_cast<const float*>(scale), L,
+                                 reinterpret_cast<int64_t*>(dst), reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_xcorr failed: " + std::to_string(e));
+          },
+          py::arg("pairs"), py::arg("span"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue the cross-correlation sums of pairs [(a, b), ..] of series of one ring over the newest min(n, span) rows "
+          "after the last refresh: scale [S] floats -> dst [K][2 lags + 1][6] int64 (n, Sx, Sy, Sxy, Sxx, Syy per lag -L .. L).")
+      .def(
           "export_joint",
           [](LongWindowSet& w, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uintptr_t bounds, uint32_t B,
              uintptr_t dst, uintptr_t stream) {
@@ -630,6 +651,26 @@ PYBIND11_MODULE(_native, m) {
           py::arg("span"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
           "Enqueue every series' autocorrelation sums over the newest min(n, span) rows after the last refresh: scale "
           "[S] floats -> dst [S][lags + 1][4] int64 (n, Sx, Sy, Sxy per lag).")
+      .def(
+          "export_xcorr",
+          [](const DeviceWindowSet& w, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uint32_t span, uintptr_t scale,
+             uint32_t L, uintptr_t dst, uintptr_t stream) {
+            std::vector<uint32_t> flat;
+            for (const auto& p : pairs) {
+              flat.push_back(p.first);
+              flat.push_back(p.second);
+            }
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_xcorr(flat.data(), uint32_t(pairs.size()), span, reinterpret_cast<const float*>(scale), L,
+                                 reinterpret_cast<int64_t*>(dst), reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_xcorr failed: " + std::to_string(e));
+          },
+          py::arg("pairs"), py::arg("span"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue the cross-correlation sums of pairs [(a, b), ..] of series of one ring over the newest min(n, span) rows "
+          "after the last refresh: scale [S] floats -> dst [K][2 lags + 1][6] int64 (n, Sx, Sy, Sxy, Sxx, Syy per lag -L .. L).")
       .def(
           "export_joint",
           [](const DeviceWindowSet& w, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uintptr_t bounds, uint32_t B,
@@ -1025,6 +1066,28 @@ PYBIND11_MODULE(_native, m) {
       py::arg("span"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
       "Autocorrelation sums of every column of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) over "
       "the newest min(n, span) rows of the window [head - n, head): scale [cols] floats -> dst [cols][lags + 1][4] int64.");
+  m.def(
+      "xcorr_ring",
+      [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n, uint32_t span,
+         uintptr_t scale, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uint32_t L, uintptr_t dst, uintptr_t stream) {
+        std::vector<uint32_t> flat;
+        for (const auto& p : pairs) {
+          flat.push_back(p.first);
+          flat.push_back(p.second);
+        }
+        int e;
+        {
+          py::gil_scoped_release nogil;
+          e = launch_xcorr_ring(reinterpret_cast<const float*>(base), stride, cols, depth, head, n, span,
+                                reinterpret_cast<const float*>(scale), flat.data(), uint32_t(pairs.size()), L,
+                                reinterpret_cast<int64_t*>(dst), reinterpret_cast<void*>(stream));
+        }
+        if (e != 0) throw std::runtime_error("xcorr_ring failed: " + std::to_string(e));
+      },
+      py::arg("base_ptr"), py::arg("stride"), py::arg("cols"), py::arg("depth"), py::arg("head"), py::arg("n"),
+      py::arg("span"), py::arg("scale_ptr"), py::arg("pairs"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
+      "Cross-correlation sums of pairs [(a, b), ..] of columns of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) "
+      "over the newest min(n, span) rows of the window [head - n, head): scale [cols] floats -> dst [K][2 lags + 1][6] int64.");
   m.def(
       "joint_ring",
       [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n,

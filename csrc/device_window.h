@@ -125,6 +125,16 @@ class DeviceWindowSet {
   // per lag, every word written (all zeroes before the first refresh and after invalidate()).
   // Returns a hipError_t (hipErrorInvalidValue before any launch or write for a bad argument).
   int export_autocorr(uint32_t span, const float* scale, uint32_t L, int64_t* dst, void* stream) const;
+  // Enqueue, after the refresh that produced it, the cross-correlation sums of K pairs of
+  // series (window_xcorr.h, defined in window_xcorr.hip) over the newest min(n, span) rows of
+  // the window of the last refresh: pairs HOST [K][2] series indices of this set, both of one
+  // ring and a != b; span, scale and L as export_autocorr; dst device [K][2L + 1][6] int64 =
+  // {n, Sx, Sy, Sxy, Sxx, Syy} per lag -L .. L, every word written (all zeroes before the first
+  // refresh and after invalidate()). A ring without a pair is not streamed. Returns a
+  // hipError_t (hipErrorInvalidValue before any launch or write for a bad argument, a pair
+  // across rings included).
+  int export_xcorr(const uint32_t* pairs, uint32_t K, uint32_t span, const float* scale, uint32_t L, int64_t* dst,
+                   void* stream) const;
   // Enqueue, after the refresh that produced it, every series' window excursions
   // (window_excursions.h, defined in window_excursions.hip) over the window of the last
   // refresh: thresholds device [num_series][K], dst device [num_series][K][8] int32 (all

@@ -275,6 +275,13 @@ class LongWindowSet {
   // int64 = {n, Sx, Sy, Sxy} per lag, every word written. Rows the host ring lost count as
   // invalid. Returns a hipError_t as export_trend does.
   int export_autocorr(uint32_t span, const float* scale, uint32_t L, int64_t* dst, void* stream);
+  // Enqueue, after the refresh that left it on the device, the cross-correlation sums of K
+  // pairs of series (window_xcorr.h, defined in window_xcorr.hip) over the newest min(n, span)
+  // rows: pairs HOST [K][2] series indices of this set, both of one ring and a != b; dst device
+  // [K][2L + 1][6] int64 = {n, Sx, Sy, Sxy, Sxx, Syy} per lag -L .. L, every word written. Rows
+  // the host ring lost count as invalid. Returns a hipError_t as export_autocorr does.
+  int export_xcorr(const uint32_t* pairs, uint32_t K, uint32_t span, const float* scale, uint32_t L, int64_t* dst,
+                   void* stream);
   // Enqueue, after the refresh that left it on the device, every series' cumulative
   // le-buckets (long_window_buckets.h, defined in long_window_buckets.hip): bounds device
   // [num_series][B], dst device [num_series][B + 1] doubles, series in set order. One

@@ -39,6 +39,7 @@ SOURCES = [
     "window_quantiles.hip",
     "window_joint.hip",
     "window_autocorr.hip",
+    "window_xcorr.hip",
     "window_excursions.hip",
     "calib.hip",
     "publish.hip",

@@ -54,7 +54,8 @@ Semantics (stated here once; the headers and everything else point here):
   arg-max returns multiples of the period of a noisy square wave, this rule its period. The
   period is in samples, not seconds, as the excursions' lengths are.
 
-Whole long windows, decimated lags, cross-correlation and a spectrum are out of scope.
+Whole long windows, decimated lags and a spectrum are out of scope; cross-correlation is
+``rocmdash.ops.window_xcorr``.
 
 Reference counterpart: none - the reference shows instant values only.
 """

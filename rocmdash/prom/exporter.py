@@ -92,7 +92,7 @@ class LocalNodeSource(SnapshotSource):
     def __init__(self, devices=None, source: str = "auto", counters: str = "auto", cfg=None,
                  window_buckets: int | None = None, window_trend: int | None = None, window_excursions=None,
                  replay=None, window_heatmap=None, window_joint=None, window_quantiles: int | None = None,
-                 window_autocorr=None):
+                 window_autocorr=None, window_xcorr=None):
         """``window_buckets`` = B > 0 (default: ``ROCMDASH_WINDOW_BUCKETS``, else off): also
         export every series' window as B cumulative le-buckets + ``+Inf``
         (``rocmdash_window_bucket``; GpuAgent.window_buckets) and their sum over the GPUs -
@@ -118,7 +118,11 @@ class LocalNodeSource(SnapshotSource):
         (``rocmdash.ops.window_autocorr.parse_autocorr``; default: ``ROCMDASH_WINDOW_AUTOCORR``, else
         off): the snapshot also carries every series' autocorrelation sums
         (GpuAgent.window_autocorr), served as JSON by ``GET /autocorr``, and ``/metrics`` gains
-        ``rocmdash_window_period_samples`` / ``_strength`` for the series that have a period."""
+        ``rocmdash_window_period_samples`` / ``_strength`` for the series that have a period.
+        ``window_xcorr`` = ``"PAIRS[/L[/SPAN]]"`` (``rocmdash.ops.window_xcorr.parse_xcorr``; default:
+        ``ROCMDASH_WINDOW_XCORR``, else off): the snapshot also carries the cross-correlation sums of
+        those pairs (GpuAgent.window_xcorr), served as JSON by ``GET /xcorr``, and ``/metrics`` gains
+        ``rocmdash_window_lag_samples`` / ``_correlation`` for the pairs that have a lag."""
         from ..runtime import native
 
         if window_excursions is None:
@@ -170,6 +174,15 @@ class LocalNodeSource(SnapshotSource):
             from ..ops.window_joint import parse_joint
 
             parse_joint(window_joint, SMI_FIELDS + CTR_FIELDS, (len(SMI_FIELDS), len(CTR_FIELDS)))
+        if window_xcorr is None:
+            window_xcorr = os.environ.get("ROCMDASH_WINDOW_XCORR", "") or None
+        if window_xcorr is not None:  # the spec, its metrics, its rings and its lags: checked before any agent exists
+            from ..config import SamplerConfig
+            from ..models.schema import CTR_FIELDS, SMI_FIELDS
+            from ..ops.window_xcorr import check_xcorr, parse_xcorr
+
+            _, xl, xs = parse_xcorr(window_xcorr, SMI_FIELDS + CTR_FIELDS, (len(SMI_FIELDS), len(CTR_FIELDS)))
+            check_xcorr(xl, xs, (cfg or SamplerConfig()).window)
         native.load()
         if counters in ("auto", "hw"):
             native.enable_counters()
@@ -196,6 +209,15 @@ class LocalNodeSource(SnapshotSource):
             except ValueError:
                 self.close()
                 raise
+        self.xcorr = None  # (pairs, L, span): rocmdash.ops.window_xcorr; GET /xcorr and the two lag gauges
+        if window_xcorr is not None:
+            from ..ops.window_xcorr import parse_xcorr
+
+            try:
+                self.xcorr = parse_xcorr(window_xcorr, self.series, [r.width for r in self.agents[0].rings])
+            except ValueError:
+                self.close()
+                raise
         for a in self.agents:
             a.start()
         self._lock = threading.Lock()
@@ -215,6 +237,8 @@ class LocalNodeSource(SnapshotSource):
         self.joint_bounds = self.agents[0].default_bucket_bounds(self.joint[1]) if self.joint else None
         # and one autocorrelation scale
         self.autocorr_scale = self.agents[0].default_autocorr_scale() if self.autocorr else None
+        # the cross-correlation quantises by the same rule
+        self.xcorr_scale = self.agents[0].default_autocorr_scale() if self.xcorr else None
 
     def collect(self):
         import torch
@@ -242,6 +266,9 @@ class LocalNodeSource(SnapshotSource):
             autocorr = None
             if self.autocorr is not None:
                 autocorr = [a.window_autocorr(self.autocorr[0], self.autocorr[1], self.autocorr_scale) for a in self.agents]
+            xcorr = None
+            if self.xcorr is not None:
+                xcorr = [a.window_xcorr(self.xcorr[0], self.xcorr[1], self.xcorr[2], self.xcorr_scale) for a in self.agents]
             quantiles = quant_age = None
             if self.quantile_columns is not None:
                 quantiles = [a.window_quantiles(self.quantile_columns) for a in self.agents]
@@ -259,6 +286,8 @@ class LocalNodeSource(SnapshotSource):
                 joint = np.stack([j.to("cpu", non_blocking=False).numpy() for j in joint])
             if autocorr is not None:
                 autocorr = np.stack([c.to("cpu", non_blocking=False).numpy() for c in autocorr])
+            if xcorr is not None:
+                xcorr = np.stack([c.to("cpu", non_blocking=False).numpy() for c in xcorr])
             if quantiles is not None:
                 quantiles = np.stack([q.to("cpu", non_blocking=False).numpy() for q in quantiles])
             now_ns = time.time_ns()
@@ -300,6 +329,8 @@ class LocalNodeSource(SnapshotSource):
             snap.window_joint_bounds = np.broadcast_to(self.joint_bounds, (len(ids),) + self.joint_bounds.shape)
         if autocorr is not None:
             snap.window_autocorr, snap.window_autocorr_span = autocorr, self.autocorr[1]
+        if xcorr is not None:
+            snap.window_xcorr, snap.window_xcorr_pairs, snap.window_xcorr_span = xcorr, tuple(self.xcorr[0]), self.xcorr[2]
         if quantiles is not None:
             snap.window_quantiles, snap.window_quantiles_age_rows = quantiles, quant_age
             snap.window_quantiles_pct = tuple(self.agents[0].pct)
@@ -450,8 +481,35 @@ def render_autocorr(snap: NodeSnapshot) -> str | None:
     return json.dumps(doc, allow_nan=False)
 
 
+def render_xcorr(snap: NodeSnapshot) -> str | None:
+    """The snapshot's window cross-correlation as the ``/xcorr`` document, None when it carries
+    none: ``{"lags": L, "span": N, "pairs": [[x, y], ..], "gpus": {gpu_id: [{"x", "y", "ccf": [2L + 1],
+    "pairs": [2L + 1], "lag_samples", "correlation"}, ..]}}``; ``ccf`` runs over lags ``-L .. L``, the
+    inner ``pairs`` is ``n_k``, the pairs of valid samples behind each lag; a lag without a
+    coefficient and a pair without a lag are null."""
+    sums = getattr(snap, "window_xcorr", None)
+    if sums is None:
+        return None
+    from ..ops.window_xcorr import cross_correlogram, pick_lag
+
+    sums = np.asarray(sums)
+    series = list(snap.window_series)
+    names = [[series[a], series[b]] for a, b in snap.window_xcorr_pairs]
+    gpus = {}
+    for g, gid in enumerate(snap.gpu_ids):
+        gpus[gid] = []
+        for k, (x, y) in enumerate(names):
+            ccf = cross_correlogram(sums[g, k])
+            lag, r = pick_lag(ccf)
+            gpus[gid].append({"x": x, "y": y, "ccf": _nullable(ccf), "pairs": [int(v) for v in sums[g, k, :, 0]],
+                              "lag_samples": lag, "correlation": r})
+    span = getattr(snap, "window_xcorr_span", None)
+    doc = {"lags": int(sums.shape[2]) // 2, "span": int(span) if span is not None else None, "pairs": names, "gpus": gpus}
+    return json.dumps(doc, allow_nan=False)
+
+
 class Exporter:
-    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``, ``/heatmap``, ``/joint``, ``/quantiles``, ``/autocorr``). With window buckets on,
+    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``, ``/heatmap``, ``/joint``, ``/quantiles``, ``/autocorr``, ``/xcorr``). With window buckets on,
     ``rocmdash_window_bucket`` / ``rocmdash_node_window_bucket`` carry exact integer counts
     for any window the source keeps: up to 32768 samples from the resident sorted windows,
     longer windows (up to 2^26) streamed from the device rings and printed from float64."""
@@ -524,6 +582,17 @@ class Exporter:
             log.exception("collect failed")
             return None
 
+    def xcorr(self) -> str | None:
+        """The ``/xcorr`` document of a fresh collection; None when the source has no window
+        cross-correlation (the option is off) or the collection failed."""
+        try:
+            snap, _ = self.source.collect()
+            return render_xcorr(snap)
+        except Exception:
+            self.errors += 1
+            log.exception("collect failed")
+            return None
+
     def autocorr(self) -> str | None:
         """The ``/autocorr`` document of a fresh collection; None when the source has no window
         autocorrelation (the option is off) or the collection failed."""
@@ -584,6 +653,12 @@ class Exporter:
                     doc = exporter.heatmap()
                     if doc is None:
                         body, ctype, code = b"no window heatmap (start with --window-heatmap PxB)\n", "text/plain", 404
+                    else:
+                        body, ctype, code = doc.encode(), "application/json", 200
+                elif self.path.split("?")[0] == "/xcorr":
+                    doc = exporter.xcorr()
+                    if doc is None:
+                        body, ctype, code = b"no window cross-correlation (start with --window-xcorr PAIRS[/L[/SPAN]])\n", "text/plain", 404
                     else:
                         body, ctype, code = doc.encode(), "application/json", 200
                 elif self.path.split("?")[0] == "/autocorr":
@@ -667,7 +742,20 @@ def main(argv=None) -> int:
                     help="also serve GET /autocorr and the rocmdash_window_period_* gauges: every series' autocorrelation at "
                          "lags 0..L (1..1024; 255, 511 and 1023 fill the kernel's blocks of 256 lags) over the newest SPAN rows of its window (a power of two in 64..1048576, "
                          "default 65536) and its period (default ROCMDASH_WINDOW_AUTOCORR, else off)")
+    ap.add_argument("--window-xcorr", default=None, metavar="PAIRS[/L[/SPAN]]",
+                    help="also serve GET /xcorr and the rocmdash_window_lag_* gauges: the cross-correlation of pairs of series "
+                         "of one ring ('default' or metricA:metricB,.., as --window-joint) at lags -L..L (1..1024, default 255) "
+                         "over the newest SPAN rows of their window (a power of two in 64..1048576, default 65536) and the "
+                         "lag of each pair (default ROCMDASH_WINDOW_XCORR, else off)")
     args = ap.parse_args(argv)
+    if args.window_xcorr is not None:
+        from ..models.schema import CTR_FIELDS, SMI_FIELDS
+        from ..ops.window_xcorr import parse_xcorr
+
+        try:
+            parse_xcorr(args.window_xcorr, SMI_FIELDS + CTR_FIELDS, (len(SMI_FIELDS), len(CTR_FIELDS)))
+        except ValueError as e:
+            ap.error(f"--window-xcorr: {e}")
     if args.window_autocorr is not None:
         from ..ops.window_autocorr import parse_autocorr
 
@@ -702,7 +790,7 @@ def main(argv=None) -> int:
         source=args.source, counters=args.counters, window_buckets=args.window_buckets, window_trend=args.window_trend,
         window_excursions=args.window_excursions, replay=args.replay, window_heatmap=args.window_heatmap,
         window_joint=args.window_joint, window_quantiles=args.window_quantiles,
-        window_autocorr=args.window_autocorr)
+        window_autocorr=args.window_autocorr, window_xcorr=args.window_xcorr)
     exp = Exporter(src)
     exp.serve(args.host, args.port)
     log.info("serving /metrics on %s:%d", args.host, exp.port)

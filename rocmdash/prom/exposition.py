@@ -140,6 +140,7 @@ def render_snapshot(snap, hostname: str = "", extra_labels: dict | None = None, 
     render_window_buckets(exp, snap, hostname, extra)
     render_window_excursions(exp, snap, hostname, extra)
     render_window_periods(exp, snap, hostname, extra)
+    render_window_lags(exp, snap, hostname, extra)
     return exp.text()
 
 
@@ -239,6 +240,37 @@ def render_window_periods(exp: Exposition, snap, hostname: str = "", extra: dict
     for lab, _, strength in found:
         exp.add("rocmdash_window_period_strength", strength, lab,
                 "Autocorrelation of a series at its period (at least 0.5; absent: no period)")
+
+
+def render_window_lags(exp: Exposition, snap, hostname: str = "", extra: dict | None = None) -> None:
+    """``rocmdash_window_lag_samples`` and ``rocmdash_window_lag_correlation``, labelled
+    ``{gpu_id, x, y}`` - and, like the period gauges, ``card_model``, ``hostname`` and the
+    exporter's extra labels - when the snapshot carries cross-correlation sums
+    (``NodeSnapshot.window_xcorr`` [N, K, 2L + 1, 6] with ``window_xcorr_pairs``) - only for the
+    pairs that have a lag (``rocmdash.ops.window_xcorr.pick_lag``). The lag is signed, positive
+    when ``y`` follows ``x``, and in samples, not seconds, as the period is."""
+    sums = getattr(snap, "window_xcorr", None)
+    if sums is None or not len(snap.window_series):
+        return
+    from ..ops.window_xcorr import cross_correlogram, pick_lag
+
+    found = []
+    for g, gid in enumerate(snap.gpu_ids):
+        base = {"gpu_id": gid, "card_model": snap.card_models[g] or ""}
+        if hostname:
+            base["hostname"] = hostname
+        base.update(extra or {})
+        for k, (a, b) in enumerate(snap.window_xcorr_pairs):
+            lag, r = pick_lag(cross_correlogram(sums[g][k]))
+            if lag is not None:
+                found.append((dict(base, x=snap.window_series[a], y=snap.window_series[b]), lag, r))
+    for lab, lag, _ in found:
+        exp.add("rocmdash_window_lag_samples", int(lag), lab,
+                "Lag of series y behind series x over the newest rows of their window, in samples: positive when y "
+                "follows x (absent: no lag)")
+    for lab, _, r in found:
+        exp.add("rocmdash_window_lag_correlation", r, lab,
+                "Correlation of the pair at its lag, signed (magnitude at least 0.5; absent: no lag)")
 
 
 def render_health(exp: Exposition, health, gpu_ids, hostname: str = "", extra: dict | None = None) -> None:

@@ -802,6 +802,56 @@ class GpuAgent:
             s += r.width
         return torch.from_numpy(out)
 
+    def window_xcorr(self, pairs=None, L=255, span=None, scale=None):
+        """Cross-correlation sums of pairs of this GPU's series, ``[K, 2L + 1, 6]`` int64: ``{n,
+        Sx, Sy, Sxy, Sxx, Syy}`` per lag ``-L .. L`` (lag k at index L + k pairs ``a[t]`` with
+        ``b[t + k]``) over the newest ``min(n, span)`` rows of the window (``span`` default
+        65536), samples quantised by ``scale`` ([S] float32; default
+        ``default_autocorr_scale()``) - ``rocmdash.ops.window_xcorr`` states the semantics; its
+        ``cross_correlogram`` and ``pick_lag`` turn the integers into the coefficient per lag and
+        the lag. ``pairs``: ``[(a, b), ..]`` series indices, both of one ring (default
+        ``default_joint_pairs()``). On a GPU the sums come from the device rings the last
+        ``refresh()`` left there (csrc/window_xcorr.hip), short or long windows alike, in stream
+        order; the scale is uploaded once per scale object and the output is reused by the next
+        call with the same pairs, the same lags and the same scale object."""
+        import torch
+
+        from ..ops.window_autocorr import check_scale
+        from ..ops.window_joint import check_pairs
+        from ..ops.window_xcorr import WORDS, check_xcorr, window_xcorr_reference
+
+        L, span = check_xcorr(L, span, self.window)
+        if pairs is None:
+            pairs = getattr(self, "_default_joint_pairs", None)
+            if pairs is None:
+                pairs = self._default_joint_pairs = self.default_joint_pairs()
+        if scale is None:
+            scale = getattr(self, "_default_autocorr_scale", None)
+            if scale is None:
+                scale = self._default_autocorr_scale = self.default_autocorr_scale()
+        S = len(self.series)
+        checked = check_pairs(pairs, [r.width for r in self.rings])  # at most 8: compared by value
+        if self.dws is not None:
+            cached = getattr(self, "_xcorr", None)
+            if cached is None or cached[0] != (checked, L) or cached[1] is not scale:
+                dev = cached[2] if cached is not None and cached[1] is scale else torch.from_numpy(check_scale(scale, S)).to(self.device)
+                out = torch.empty((len(checked), 2 * L + 1, WORDS), dtype=torch.int64, device=self.device)
+                cached = self._xcorr = ((checked, L), scale, dev, out)
+            _, _, dev, out = cached
+            self.dws.export_xcorr(checked, span, dev.data_ptr(), L, out.data_ptr(), _current_raw_stream(self.device_index))
+            return out
+        sc = check_scale(scale, S)
+        out, s = np.zeros((len(checked), 2 * L + 1, WORDS), dtype=np.int64), 0
+        for r in self.rings:
+            mine = [k for k, (a, _) in enumerate(checked) if s <= a < s + r.width]
+            if mine:
+                rows, _ = r.window(self.window)
+                rows = np.asarray(rows, dtype=np.float32).reshape(-1, r.width)
+                out[mine] = window_xcorr_reference(rows, [(checked[k][0] - s, checked[k][1] - s) for k in mine],
+                                                   sc[s : s + r.width], L, span)
+            s += r.width
+        return torch.from_numpy(out)
+
     def default_excursion_thresholds(self, fractions=(0.5, 0.75, 0.9)) -> np.ndarray:
         """``[S, K]`` float32 thresholds of this GPU's series: ``fractions`` of each series'
         axis, the axis of ``default_bucket_bounds``

@@ -245,6 +245,32 @@ def window_autocorr_figures(snap: NodeSnapshot, selected=None, height: int = 220
     return figs
 
 
+def window_xcorr_figures(snap: NodeSnapshot, selected=None, height: int = 220) -> list | None:
+    """[(key, Figure)]: per selected GPU and pair the cross-correlogram
+    (``rocmdash.ops.window_xcorr``) the snapshot carries, as a line over the lag ``-L .. L`` with a
+    zero line and a marker at the pair's lag (None if the snapshot carries none)."""
+    sums = getattr(snap, "window_xcorr", None)
+    pairs = getattr(snap, "window_xcorr_pairs", None)
+    if sums is None or pairs is None:
+        return None
+    from ..ops.window_xcorr import cross_correlogram, pick_lag
+    from ..viz.figures import create_xcorr
+
+    series = list(snap.window_series)
+    short = lambda m: m[len("amd_gpu_"):] if m.startswith("amd_gpu_") else m  # noqa: E731
+    sel = set(str(g) for g in selected) if selected is not None else None
+    figs = []
+    for g, gid in enumerate(snap.gpu_ids):
+        if sel is not None and gid not in sel:
+            continue
+        for k, (a, b) in enumerate(pairs):
+            x, y = short(series[a]), short(series[b])
+            ccf = cross_correlogram(sums[g][k])
+            lag, _ = pick_lag(ccf)
+            figs.append((f"plot_xcorr_{x}_{y}_{gid}_", create_xcorr(f"GPU {gid}: {y} after {x}", ccf, lag, x, y, height)))
+    return figs
+
+
 def window_heatmap_figures(snap: NodeSnapshot, selected=None, height: int = 220) -> list | None:
     """[(key, Figure)]: per selected GPU the window heatmap (``rocmdash.ops.window_heatmap``)
     of every panel metric the snapshot's heatmap has - the metrics and the seconds of
@@ -351,7 +377,7 @@ def xcd_table(snap: NodeSnapshot, selected=None) -> dict | None:
 def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xcd: dict | None = None,
                   buckets: dict | None = None, trend: list | None = None, excursions: dict | None = None,
                   heatmap: list | None = None, joint: list | None = None, quantiles: list | None = None,
-                  autocorr: list | None = None) -> None:
+                  autocorr: list | None = None, xcorr: list | None = None) -> None:
     st.subheader("Average Metrics (Selected GPUs)")
     avg_cols = st.columns(4)
     for col, (key, spec) in zip(avg_cols, frame.avg_panels):
@@ -398,6 +424,12 @@ def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xc
         st.subheader("Window Autocorrelation (acf over the lag in samples; the marker is the period)")
         for i in range(0, len(autocorr), 4):
             for col, (key, fig) in zip(st.columns(4), autocorr[i : i + 4]):
+                with col:
+                    st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
+    if extended and xcorr:
+        st.subheader("Window Cross-correlation (r over the lag in samples; right of zero the second series follows)")
+        for i in range(0, len(xcorr), 4):
+            for col, (key, fig) in zip(st.columns(4), xcorr[i : i + 4]):
                 with col:
                     st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
     if extended and heatmap:
@@ -492,7 +524,8 @@ def main(max_refreshes: int | None = None, data_source: str | None = None) -> No
                               window_heatmap_figures(snap, st.session_state.selected_gpus) if extended else None,
                               window_joint_figures(snap, st.session_state.selected_gpus) if extended else None,
                               window_quantile_figures(snap, st.session_state.selected_gpus) if extended else None,
-                              window_autocorr_figures(snap, st.session_state.selected_gpus) if extended else None)
+                              window_autocorr_figures(snap, st.session_state.selected_gpus) if extended else None,
+                              window_xcorr_figures(snap, st.session_state.selected_gpus) if extended else None)
         n += 1
         if max_refreshes is not None and n >= max_refreshes:
             break

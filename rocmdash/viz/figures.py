@@ -532,6 +532,30 @@ def create_autocorr(title, acf, names=None, periods=None, height=220) -> Figure:
     return Figure(traces, layout)
 
 
+def create_xcorr(title, ccf, lag=None, x_name=None, y_name=None, height=220) -> Figure:
+    """A window cross-correlogram (``rocmdash.ops.window_xcorr``) as one Plotly ``scatter`` line
+    over the lag in samples, ``-L .. L``, with a zero line and a marker at the pair's lag.
+    ``ccf``: ``[2L + 1]`` (NaN: a lag without a coefficient, drawn as a gap); ``lag``: the pair's
+    lag in samples (positive: ``y_name`` follows ``x_name``) or None. No reference counterpart."""
+    y = [None if v is None or v != v else _num(v) for v in ccf]
+    L = len(y) // 2
+    name = f"{y_name} after {x_name}" if x_name and y_name else "ccf"
+    traces = [{"mode": "lines", "name": name, "x": list(range(-L, len(y) - L)), "y": y, "type": "scatter"}]
+    if lag is not None and -L <= int(lag) <= L and y[L + int(lag)] is not None:
+        traces.append({"marker": {"size": 9, "symbol": "diamond"}, "mode": "markers", "name": f"lag {int(lag)}",
+                       "x": [int(lag)], "y": [y[L + int(lag)]], "type": "scatter"})
+    layout = {
+        "title": {"text": title},
+        "xaxis": {"title": {"text": "lag (samples)"}},
+        "yaxis": {"range": [-1, 1], "title": {"text": "r"}},
+        "shapes": [{"type": "line", "x0": 0, "x1": 0, "y0": -1, "y1": 1, "line": {"width": 1, "dash": "dot"}}],
+        "margin": {"l": 40, "r": 20, "t": 40, "b": 40},
+        "height": _num(height),
+        "showlegend": False,
+    }
+    return Figure(traces, layout)
+
+
 def create_joint(title, le_x, le_y, counts, x_title=None, y_title=None, height=260) -> Figure:
     """A window joint histogram (``rocmdash.ops.window_joint``) as one Plotly ``heatmap`` trace:
     x = each bin's upper bound of the pair's first series, y = of its second, z = the rows in

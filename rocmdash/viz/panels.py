@@ -133,6 +133,12 @@ class NodeSnapshot:
     # [N, S, L + 1, 4] int64 = {n, Sx, Sy, Sxy} per lag, and the span they were taken over
     window_autocorr: np.ndarray | None = None
     window_autocorr_span: int | None = None
+    # Window cross-correlation sums (rocmdash.ops.window_xcorr), when computed: per GPU
+    # [N, K, 2L + 1, 6] int64 = {n, Sx, Sy, Sxy, Sxx, Syy} per lag -L .. L, the K pairs as (a, b)
+    # indices into window_series, and the span they were taken over
+    window_xcorr: np.ndarray | None = None
+    window_xcorr_pairs: tuple | None = None
+    window_xcorr_span: int | None = None
     # Window quantile trend (rocmdash.ops.window_quantiles), when computed: per GPU
     # [N, S, P + 1, 4] - the three percentiles window_quantiles_pct and their count of each of
     # the trend's P + 1 column slots - and the slots' ages as for the trend
