@@ -19,6 +19,7 @@
 #include "window_excursions.h"
 #include "window_heatmap.h"
 #include "window_joint.h"
+#include "window_periods.h"
 #include "window_quantiles.h"
 #include "window_trend.h"
 #include "window_xcorr.h"
@@ -413,6 +414,20 @@ PYBIND11_MODULE(_native, m) {
           "Enqueue every series' autocorrelation sums over the newest min(n, span) rows after the last refresh: scale "
           "[S] floats -> dst [S][lags + 1][4] int64 (n, Sx, Sy, Sxy per lag).")
       .def(
+          "export_periods",
+          [](LongWindowSet& w, uint32_t span, uint32_t P, uintptr_t scale, uint32_t L, uintptr_t dst, uintptr_t stream) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_periods(span, P, reinterpret_cast<const float*>(scale), L, reinterpret_cast<int64_t*>(dst),
+                                   reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_periods failed: " + std::to_string(e));
+          },
+          py::arg("span"), py::arg("columns"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue every series' window period trend after the last refresh: the autocorrelation's sums per trend slot of "
+          "the newest min(n, span) rows: scale [S] floats -> dst [S][columns + 1][lags + 1][4] int64.")
+      .def(
           "export_xcorr",
           [](LongWindowSet& w, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uint32_t span, uintptr_t scale,
              uint32_t L, uintptr_t dst, uintptr_t stream) {
@@ -651,6 +666,20 @@ PYBIND11_MODULE(_native, m) {
           py::arg("span"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
           "Enqueue every series' autocorrelation sums over the newest min(n, span) rows after the last refresh: scale "
           "[S] floats -> dst [S][lags + 1][4] int64 (n, Sx, Sy, Sxy per lag).")
+      .def(
+          "export_periods",
+          [](const DeviceWindowSet& w, uint32_t span, uint32_t P, uintptr_t scale, uint32_t L, uintptr_t dst, uintptr_t stream) {
+            int e;
+            {
+              py::gil_scoped_release nogil;
+              e = w.export_periods(span, P, reinterpret_cast<const float*>(scale), L, reinterpret_cast<int64_t*>(dst),
+                                   reinterpret_cast<void*>(stream));
+            }
+            if (e != 0) throw std::runtime_error("export_periods failed: " + std::to_string(e));
+          },
+          py::arg("span"), py::arg("columns"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
+          "Enqueue every series' window period trend after the last refresh: the autocorrelation's sums per trend slot of "
+          "the newest min(n, span) rows: scale [S] floats -> dst [S][columns + 1][lags + 1][4] int64.")
       .def(
           "export_xcorr",
           [](const DeviceWindowSet& w, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uint32_t span, uintptr_t scale,
@@ -1049,6 +1078,25 @@ PYBIND11_MODULE(_native, m) {
       py::arg("stream"),
       "Window heatmap of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) whose window is rows "
       "[head - n, head): bounds [cols][B] floats -> dst [cols][columns + 1][B + 1] int32 (per-bin counts per slot).");
+  m.def(
+      "periods_ring",
+      [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n, uint32_t span, uint32_t P,
+         uintptr_t scale, uint32_t L, uintptr_t dst, uint32_t split, uintptr_t stream) {
+        int e;
+        {
+          py::gil_scoped_release nogil;
+          e = launch_periods_ring(reinterpret_cast<const float*>(base), stride, cols, depth, head, n, span, P,
+                                  reinterpret_cast<const float*>(scale), L, reinterpret_cast<int64_t*>(dst), split,
+                                  reinterpret_cast<void*>(stream));
+        }
+        if (e != 0) throw std::runtime_error("periods_ring failed: " + std::to_string(e));
+      },
+      py::arg("base_ptr"), py::arg("stride"), py::arg("cols"), py::arg("depth"), py::arg("head"), py::arg("n"),
+      py::arg("span"), py::arg("columns"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("split"),
+      py::arg("stream"),
+      "Window period trend of every column of one time-major ring [depth][stride] (row r at slot r & (depth - 1)): the "
+      "autocorrelation's sums per trend slot of the newest min(n, span) rows of the window [head - n, head): scale [cols] "
+      "floats -> dst [cols][columns + 1][lags + 1][4] int64. split 0: the plan decides; else workgroups per slot.");
   m.def(
       "autocorr_ring",
       [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n, uint32_t span,

@@ -125,6 +125,15 @@ class DeviceWindowSet {
   // per lag, every word written (all zeroes before the first refresh and after invalidate()).
   // Returns a hipError_t (hipErrorInvalidValue before any launch or write for a bad argument).
   int export_autocorr(uint32_t span, const float* scale, uint32_t L, int64_t* dst, void* stream) const;
+  // Enqueue, after the refresh that produced it, every series' window period trend
+  // (window_periods.h, defined in window_periods.hip): the autocorrelation's sums per trend
+  // slot of the newest min(n, span) rows, span <= window() a power of two in [2^9, 2^20], P
+  // columns (a power of two in [8, 64]) of span / P rows, 1 <= L <= min(1024, span / P / 2),
+  // P (L + 1) <= 16384; scale as export_autocorr; dst device [num_series][P + 1][L + 1][4]
+  // int64, 16-byte aligned, every word written (all zeroes before the first refresh and after
+  // invalidate()). Returns a hipError_t (hipErrorInvalidValue before any launch or write for a
+  // bad argument).
+  int export_periods(uint32_t span, uint32_t P, const float* scale, uint32_t L, int64_t* dst, void* stream) const;
   // Enqueue, after the refresh that produced it, the cross-correlation sums of K pairs of
   // series (window_xcorr.h, defined in window_xcorr.hip) over the newest min(n, span) rows of
   // the window of the last refresh: pairs HOST [K][2] series indices of this set, both of one

@@ -275,6 +275,12 @@ class LongWindowSet {
   // int64 = {n, Sx, Sy, Sxy} per lag, every word written. Rows the host ring lost count as
   // invalid. Returns a hipError_t as export_trend does.
   int export_autocorr(uint32_t span, const float* scale, uint32_t L, int64_t* dst, void* stream);
+  // Enqueue, after the refresh that left it on the device, every series' window period trend
+  // (window_periods.h, defined in window_periods.hip): the autocorrelation's sums per trend
+  // slot of the newest min(n, span) rows, P columns of span / P rows, span <= window(); dst
+  // device [num_series][P + 1][L + 1][4] int64, 16-byte aligned, every word written. Rows the
+  // host ring lost count as invalid. Returns a hipError_t as export_autocorr does.
+  int export_periods(uint32_t span, uint32_t P, const float* scale, uint32_t L, int64_t* dst, void* stream);
   // Enqueue, after the refresh that left it on the device, the cross-correlation sums of K
   // pairs of series (window_xcorr.h, defined in window_xcorr.hip) over the newest min(n, span)
   // rows: pairs HOST [K][2] series indices of this set, both of one ring and a != b; dst device

@@ -40,6 +40,7 @@ SOURCES = [
     "window_joint.hip",
     "window_autocorr.hip",
     "window_xcorr.hip",
+    "window_periods.hip",
     "window_excursions.hip",
     "calib.hip",
     "publish.hip",

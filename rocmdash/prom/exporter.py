@@ -92,7 +92,7 @@ class LocalNodeSource(SnapshotSource):
     def __init__(self, devices=None, source: str = "auto", counters: str = "auto", cfg=None,
                  window_buckets: int | None = None, window_trend: int | None = None, window_excursions=None,
                  replay=None, window_heatmap=None, window_joint=None, window_quantiles: int | None = None,
-                 window_autocorr=None, window_xcorr=None):
+                 window_autocorr=None, window_xcorr=None, window_periods=None):
         """``window_buckets`` = B > 0 (default: ``ROCMDASH_WINDOW_BUCKETS``, else off): also
         export every series' window as B cumulative le-buckets + ``+Inf``
         (``rocmdash_window_bucket``; GpuAgent.window_buckets) and their sum over the GPUs -
@@ -122,7 +122,11 @@ class LocalNodeSource(SnapshotSource):
         ``window_xcorr`` = ``"PAIRS[/L[/SPAN]]"`` (``rocmdash.ops.window_xcorr.parse_xcorr``; default:
         ``ROCMDASH_WINDOW_XCORR``, else off): the snapshot also carries the cross-correlation sums of
         those pairs (GpuAgent.window_xcorr), served as JSON by ``GET /xcorr``, and ``/metrics`` gains
-        ``rocmdash_window_lag_samples`` / ``_correlation`` for the pairs that have a lag."""
+        ``rocmdash_window_lag_samples`` / ``_correlation`` for the pairs that have a lag.
+        ``window_periods`` = ``"P[/L[/SPAN]]"`` (``rocmdash.ops.window_periods.parse_periods``; default:
+        ``ROCMDASH_WINDOW_PERIODS``, else off): the snapshot also carries every series' autocorrelation
+        sums per trend column of the newest SPAN rows (GpuAgent.window_periods), served as JSON by
+        ``GET /periods`` - never in ``/metrics``."""
         from ..runtime import native
 
         if window_excursions is None:
@@ -167,6 +171,14 @@ class LocalNodeSource(SnapshotSource):
             from ..ops.window_autocorr import check_autocorr, parse_autocorr
 
             self.autocorr = check_autocorr(*parse_autocorr(window_autocorr), (cfg or SamplerConfig()).window)
+        if window_periods is None:
+            window_periods = os.environ.get("ROCMDASH_WINDOW_PERIODS", "") or None
+        self.periods = None  # (P, L, span): rocmdash.ops.window_periods; GET /periods
+        if window_periods is not None:  # checked before any agent starts its samplers
+            from ..config import SamplerConfig
+            from ..ops.window_periods import parse_periods
+
+            self.periods = parse_periods(window_periods, (cfg or SamplerConfig()).window)
         if window_joint is None:
             window_joint = os.environ.get("ROCMDASH_WINDOW_JOINT", "") or None
         if window_joint is not None:  # the spec, its metrics and its rings: checked before any agent exists
@@ -239,6 +251,8 @@ class LocalNodeSource(SnapshotSource):
         self.autocorr_scale = self.agents[0].default_autocorr_scale() if self.autocorr else None
         # the cross-correlation quantises by the same rule
         self.xcorr_scale = self.agents[0].default_autocorr_scale() if self.xcorr else None
+        # and so does the period trend
+        self.periods_scale = self.agents[0].default_autocorr_scale() if self.periods else None
 
     def collect(self):
         import torch
@@ -269,6 +283,11 @@ class LocalNodeSource(SnapshotSource):
             xcorr = None
             if self.xcorr is not None:
                 xcorr = [a.window_xcorr(self.xcorr[0], self.xcorr[1], self.xcorr[2], self.xcorr_scale) for a in self.agents]
+            periods = periods_age = None
+            if self.periods is not None:
+                periods = [a.window_periods(self.periods[0], self.periods[1], self.periods[2], self.periods_scale)
+                           for a in self.agents]
+                periods_age = self.agents[0].periods_age_rows(self.periods[0], self.periods[2])
             quantiles = quant_age = None
             if self.quantile_columns is not None:
                 quantiles = [a.window_quantiles(self.quantile_columns) for a in self.agents]
@@ -288,6 +307,8 @@ class LocalNodeSource(SnapshotSource):
                 autocorr = np.stack([c.to("cpu", non_blocking=False).numpy() for c in autocorr])
             if xcorr is not None:
                 xcorr = np.stack([c.to("cpu", non_blocking=False).numpy() for c in xcorr])
+            if periods is not None:
+                periods = np.stack([c.to("cpu", non_blocking=False).numpy() for c in periods])
             if quantiles is not None:
                 quantiles = np.stack([q.to("cpu", non_blocking=False).numpy() for q in quantiles])
             now_ns = time.time_ns()
@@ -331,6 +352,8 @@ class LocalNodeSource(SnapshotSource):
             snap.window_autocorr, snap.window_autocorr_span = autocorr, self.autocorr[1]
         if xcorr is not None:
             snap.window_xcorr, snap.window_xcorr_pairs, snap.window_xcorr_span = xcorr, tuple(self.xcorr[0]), self.xcorr[2]
+        if periods is not None:
+            snap.window_periods, snap.window_periods_span, snap.window_periods_age_rows = periods, self.periods[2], periods_age
         if quantiles is not None:
             snap.window_quantiles, snap.window_quantiles_age_rows = quantiles, quant_age
             snap.window_quantiles_pct = tuple(self.agents[0].pct)
@@ -481,6 +504,30 @@ def render_autocorr(snap: NodeSnapshot) -> str | None:
     return json.dumps(doc, allow_nan=False)
 
 
+def render_periods(snap: NodeSnapshot) -> str | None:
+    """The snapshot's window period trend as the ``/periods`` document, None when it carries none:
+    ``{"columns": P, "lags": L, "span": N, "age_rows": [P + 1], "series": [...], "gpus": {gpu_id:
+    {metric: {"period_samples": [P + 1], "strength": [P + 1], "rows": [P + 1]}}}}``; ``rows`` is
+    ``n_0``, the valid samples of each slot; a slot without a period and the age of an empty slot
+    are null."""
+    sums = getattr(snap, "window_periods", None)
+    if sums is None:
+        return None
+    from ..ops.window_periods import slot_periods
+
+    sums = np.asarray(sums)
+    series = list(snap.window_series)
+    gpus = {}
+    for g, gid in enumerate(snap.gpu_ids):
+        period, strength, valid = slot_periods(sums[g])
+        gpus[gid] = {m: {"period_samples": [None if v != v else int(v) for v in period[s]], "strength": _nullable(strength[s]),
+                         "rows": [int(v) for v in valid[s]]} for s, m in enumerate(series)}
+    span, age = getattr(snap, "window_periods_span", None), getattr(snap, "window_periods_age_rows", None)
+    doc = {"columns": int(sums.shape[2]) - 1, "lags": int(sums.shape[3]) - 1, "span": int(span) if span is not None else None,
+           "age_rows": _nullable(age) if age is not None else None, "series": series, "gpus": gpus}
+    return json.dumps(doc, allow_nan=False)
+
+
 def render_xcorr(snap: NodeSnapshot) -> str | None:
     """The snapshot's window cross-correlation as the ``/xcorr`` document, None when it carries
     none: ``{"lags": L, "span": N, "pairs": [[x, y], ..], "gpus": {gpu_id: [{"x", "y", "ccf": [2L + 1],
@@ -509,7 +556,7 @@ def render_xcorr(snap: NodeSnapshot) -> str | None:
 
 
 class Exporter:
-    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``, ``/heatmap``, ``/joint``, ``/quantiles``, ``/autocorr``, ``/xcorr``). With window buckets on,
+    """Serves a ``SnapshotSource`` as ``/metrics`` (and ``/trend``, ``/heatmap``, ``/joint``, ``/quantiles``, ``/autocorr``, ``/xcorr``, ``/periods``). With window buckets on,
     ``rocmdash_window_bucket`` / ``rocmdash_node_window_bucket`` carry exact integer counts
     for any window the source keeps: up to 32768 samples from the resident sorted windows,
     longer windows (up to 2^26) streamed from the device rings and printed from float64."""
@@ -593,6 +640,17 @@ class Exporter:
             log.exception("collect failed")
             return None
 
+    def periods(self) -> str | None:
+        """The ``/periods`` document of a fresh collection; None when the source has no window
+        period trend (the option is off) or the collection failed."""
+        try:
+            snap, _ = self.source.collect()
+            return render_periods(snap)
+        except Exception:
+            self.errors += 1
+            log.exception("collect failed")
+            return None
+
     def autocorr(self) -> str | None:
         """The ``/autocorr`` document of a fresh collection; None when the source has no window
         autocorrelation (the option is off) or the collection failed."""
@@ -659,6 +717,12 @@ class Exporter:
                     doc = exporter.xcorr()
                     if doc is None:
                         body, ctype, code = b"no window cross-correlation (start with --window-xcorr PAIRS[/L[/SPAN]])\n", "text/plain", 404
+                    else:
+                        body, ctype, code = doc.encode(), "application/json", 200
+                elif self.path.split("?")[0] == "/periods":
+                    doc = exporter.periods()
+                    if doc is None:
+                        body, ctype, code = b"no window period trend (start with --window-periods P[/L[/SPAN]])\n", "text/plain", 404
                     else:
                         body, ctype, code = doc.encode(), "application/json", 200
                 elif self.path.split("?")[0] == "/autocorr":
@@ -747,7 +811,19 @@ def main(argv=None) -> int:
                          "of one ring ('default' or metricA:metricB,.., as --window-joint) at lags -L..L (1..1024, default 255) "
                          "over the newest SPAN rows of their window (a power of two in 64..1048576, default 65536) and the "
                          "lag of each pair (default ROCMDASH_WINDOW_XCORR, else off)")
+    ap.add_argument("--window-periods", default=None, metavar="P[/L[/SPAN]]",
+                    help="also serve GET /periods: every series' period per trend column - the autocorrelation at lags 0..L "
+                         "(default 255; at most half a column) of each of P + 1 columns (a power of two in 8..64) of the "
+                         "newest SPAN rows of its window (a power of two in 512..1048576, default min(window, 65536)) "
+                         "(default ROCMDASH_WINDOW_PERIODS, else off)")
     args = ap.parse_args(argv)
+    if args.window_periods is not None:
+        from ..ops.window_periods import parse_periods
+
+        try:
+            parse_periods(args.window_periods, config.SamplerConfig().window)
+        except ValueError as e:
+            ap.error(f"--window-periods: {e}")
     if args.window_xcorr is not None:
         from ..models.schema import CTR_FIELDS, SMI_FIELDS
         from ..ops.window_xcorr import parse_xcorr
@@ -790,7 +866,7 @@ def main(argv=None) -> int:
         source=args.source, counters=args.counters, window_buckets=args.window_buckets, window_trend=args.window_trend,
         window_excursions=args.window_excursions, replay=args.replay, window_heatmap=args.window_heatmap,
         window_joint=args.window_joint, window_quantiles=args.window_quantiles,
-        window_autocorr=args.window_autocorr, window_xcorr=args.window_xcorr)
+        window_autocorr=args.window_autocorr, window_xcorr=args.window_xcorr, window_periods=args.window_periods)
     exp = Exporter(src)
     exp.serve(args.host, args.port)
     log.info("serving /metrics on %s:%d", args.host, exp.port)

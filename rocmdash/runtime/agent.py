@@ -802,6 +802,58 @@ class GpuAgent:
             s += r.width
         return torch.from_numpy(out)
 
+    def window_periods(self, P, L=255, span=None, scale=None):
+        """Every series' period trend sums, ``[S, P + 1, L + 1, 4]`` int64: the autocorrelation's
+        ``{n, Sx, Sy, Sxy}`` per lag ``0 .. L`` of each of the trend's ``P + 1`` slots of the
+        newest ``min(n, span)`` rows (``span`` default ``min(window, 65536)``), samples quantised
+        by ``scale`` ([S] float32; default ``default_autocorr_scale()``) -
+        ``rocmdash.ops.window_periods`` states the semantics; its ``slot_periods`` turns the
+        integers into a period per slot and ``periods_age_rows`` gives the x axis. On a GPU the
+        sums come from the device rings the last ``refresh()`` left there
+        (csrc/window_periods.hip), short or long windows alike, in stream order; the scale is
+        uploaded once per scale object and the output is reused by the next call with the same
+        columns, lags and scale object."""
+        import torch
+
+        from ..ops.window_periods import check_periods, check_scale, window_periods_reference
+
+        P, L, span = check_periods(P, L, span, self.window)
+        if scale is None:
+            scale = getattr(self, "_default_autocorr_scale", None)
+            if scale is None:
+                scale = self._default_autocorr_scale = self.default_autocorr_scale()
+        S = len(self.series)
+        if self.dws is not None:
+            cached = getattr(self, "_periods", None)
+            if cached is None or cached[0] != (P, L) or cached[1] is not scale:
+                dev = cached[2] if cached is not None and cached[1] is scale else torch.from_numpy(check_scale(scale, S)).to(self.device)
+                out = torch.empty((S, P + 1, L + 1, 4), dtype=torch.int64, device=self.device)
+                cached = self._periods = ((P, L), scale, dev, out)
+            _, _, dev, out = cached
+            self.dws.export_periods(span, P, dev.data_ptr(), L, out.data_ptr(), _current_raw_stream(self.device_index))
+            return out
+        sc = check_scale(scale, S)
+        out, s = np.zeros((S, P + 1, L + 1, 4), dtype=np.int64), 0
+        for r in self.rings:
+            for _ in range(8):  # the window and the head it ends at, with no row pushed in between
+                head = int(r.head)
+                rows, _ = r.window(self.window)
+                if int(r.head) == head:
+                    break
+            rows = np.asarray(rows, dtype=np.float32).reshape(-1, r.width)
+            out[s : s + r.width] = window_periods_reference(rows, sc[s : s + r.width], head, self.window, P, L, span)
+            s += r.width
+        return torch.from_numpy(out)
+
+    def periods_age_rows(self, P, span=None, ring_index: int = 0) -> np.ndarray:
+        """``[P + 1]``: rows between each period slot's last row and the newest row of ring
+        ``ring_index`` (NaN: an empty slot), from the ring's head now."""
+        from ..ops.window_periods import check_periods, periods_age_rows
+
+        P, _, span = check_periods(P, 1, span, self.window)
+        h = int(self.rings[ring_index].head)
+        return periods_age_rows(h, min(h, self.window), P, span)
+
     def window_xcorr(self, pairs=None, L=255, span=None, scale=None):
         """Cross-correlation sums of pairs of this GPU's series, ``[K, 2L + 1, 6]`` int64: ``{n,
         Sx, Sy, Sxy, Sxx, Syy}`` per lag ``-L .. L`` (lag k at index L + k pairs ``a[t]`` with

@@ -245,6 +245,40 @@ def window_autocorr_figures(snap: NodeSnapshot, selected=None, height: int = 220
     return figs
 
 
+def window_periods_figures(snap: NodeSnapshot, selected=None, height: int = 220) -> list | None:
+    """[(key, Figure)]: per selected GPU the window period trend (``rocmdash.ops.window_periods``)
+    of every panel metric the snapshot's has - the metrics and the seconds of
+    ``window_trend_figures`` - as the period of each slot over time (None if the snapshot carries
+    none)."""
+    sums = getattr(snap, "window_periods", None)
+    age = getattr(snap, "window_periods_age_rows", None)
+    if sums is None or age is None:
+        return None
+    from ..models.schema import CTR_FIELDS
+    from ..ops.window_periods import slot_periods
+    from ..viz.figures import create_periods
+    from ..viz.panels import EXTENDED_PANELS, POWER, TEMP, UTIL
+
+    cfg = config.SamplerConfig()
+    index = {s: i for i, s in enumerate(snap.window_series)}
+    sel = set(str(g) for g in selected) if selected is not None else None
+    figs = []
+    for g, gid in enumerate(snap.gpu_ids):
+        if sel is not None and gid not in sel:
+            continue
+        panels = [(UTIL, "GPU Utilization (%)", "gpu_util", 100.0), (TEMP, "Temperature (°C)", "temp", 100.0),
+                  (POWER, "Power Usage (W)", "power", snap.power_max(gid))] + list(EXTENDED_PANELS)
+        for col, title, key, _ in panels:
+            s = index.get(col)
+            if s is None:
+                continue
+            seconds = 1.0 / (cfg.counter_hz if col in CTR_FIELDS else cfg.smi_hz)
+            period, strength, _ = slot_periods(sums[g][s : s + 1])
+            figs.append((f"plot_periods_{key}_{gid}_",
+                         create_periods(f"GPU {gid}: {title}", [a * seconds for a in age], period[0], strength[0], height)))
+    return figs
+
+
 def window_xcorr_figures(snap: NodeSnapshot, selected=None, height: int = 220) -> list | None:
     """[(key, Figure)]: per selected GPU and pair the cross-correlogram
     (``rocmdash.ops.window_xcorr``) the snapshot carries, as a line over the lag ``-L .. L`` with a
@@ -377,7 +411,7 @@ def xcd_table(snap: NodeSnapshot, selected=None) -> dict | None:
 def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xcd: dict | None = None,
                   buckets: dict | None = None, trend: list | None = None, excursions: dict | None = None,
                   heatmap: list | None = None, joint: list | None = None, quantiles: list | None = None,
-                  autocorr: list | None = None, xcorr: list | None = None) -> None:
+                  autocorr: list | None = None, xcorr: list | None = None, periods: list | None = None) -> None:
     st.subheader("Average Metrics (Selected GPUs)")
     avg_cols = st.columns(4)
     for col, (key, spec) in zip(avg_cols, frame.avg_panels):
@@ -424,6 +458,12 @@ def _render_frame(st, frame, extended: bool, node_window: dict | None = None, xc
         st.subheader("Window Autocorrelation (acf over the lag in samples; the marker is the period)")
         for i in range(0, len(autocorr), 4):
             for col, (key, fig) in zip(st.columns(4), autocorr[i : i + 4]):
+                with col:
+                    st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
+    if extended and periods:
+        st.subheader("Window Period Trend (each column's period in samples; fainter markers are weaker periods)")
+        for i in range(0, len(periods), 4):
+            for col, (key, fig) in zip(st.columns(4), periods[i : i + 4]):
                 with col:
                     st.plotly_chart(fig.to_dict(), use_container_width=True, key=key)
     if extended and xcorr:
@@ -525,7 +565,8 @@ def main(max_refreshes: int | None = None, data_source: str | None = None) -> No
                               window_joint_figures(snap, st.session_state.selected_gpus) if extended else None,
                               window_quantile_figures(snap, st.session_state.selected_gpus) if extended else None,
                               window_autocorr_figures(snap, st.session_state.selected_gpus) if extended else None,
-                              window_xcorr_figures(snap, st.session_state.selected_gpus) if extended else None)
+                              window_xcorr_figures(snap, st.session_state.selected_gpus) if extended else None,
+                              window_periods_figures(snap, st.session_state.selected_gpus) if extended else None)
         n += 1
         if max_refreshes is not None and n >= max_refreshes:
             break

@@ -532,6 +532,36 @@ def create_autocorr(title, acf, names=None, periods=None, height=220) -> Figure:
     return Figure(traces, layout)
 
 
+def create_periods(title, age_s, period, strength=None, height=220) -> Figure:
+    """A window period trend (``rocmdash.ops.window_periods``) as one Plotly ``scatter`` trace of
+    lines and markers over the trend's x axis (seconds before the newest sample, negative: time
+    runs left to right): y = each slot's period in samples. ``age_s``, ``period``: one entry per
+    slot, oldest first; ``strength``: the period's acf per slot, shown as the hover text and as the
+    marker's opacity (0.25 at the rule's threshold of 0.5 and below, 1 at 1). A slot whose age is
+    NaN or that has no period is a null point - a gap, never a line drawn across it. No reference
+    counterpart."""
+    xs, ys, text, alpha = [], [], [], []
+    strength = list(strength) if strength is not None else [None] * len(age_s)
+    for a, p, r in zip(age_s, period, strength):
+        a, p, r = _num(a), _num(p), _num(r)
+        gap = a is None or p is None
+        xs.append(None if a is None else -a)
+        ys.append(None if gap else p)
+        text.append(None if gap or r is None else f"strength {r:.2f}")
+        alpha.append(1.0 if gap or r is None else min(1.0, max(0.25, 0.25 + 1.5 * (r - 0.5))))
+    trace = {"connectgaps": False, "marker": {"opacity": alpha, "size": 7}, "mode": "lines+markers", "name": "period",
+             "text": text, "x": xs, "y": ys, "type": "scatter"}
+    layout = {
+        "title": {"text": title},
+        "xaxis": {"title": {"text": "seconds"}, "showgrid": True, "gridcolor": "lightgray"},
+        "yaxis": {"rangemode": "tozero", "title": {"text": "period (samples)"}},
+        "margin": {"l": 40, "r": 20, "t": 40, "b": 40},
+        "height": _num(height),
+        "showlegend": False,
+    }
+    return Figure([trace], layout)
+
+
 def create_xcorr(title, ccf, lag=None, x_name=None, y_name=None, height=220) -> Figure:
     """A window cross-correlogram (``rocmdash.ops.window_xcorr``) as one Plotly ``scatter`` line
     over the lag in samples, ``-L .. L``, with a zero line and a marker at the pair's lag.

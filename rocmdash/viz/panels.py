@@ -139,6 +139,12 @@ class NodeSnapshot:
     window_xcorr: np.ndarray | None = None
     window_xcorr_pairs: tuple | None = None
     window_xcorr_span: int | None = None
+    # Window period trend (rocmdash.ops.window_periods), when computed: per GPU
+    # [N, S, P + 1, L + 1, 4] int64 - the autocorrelation's sums of each of the P + 1 column
+    # slots of the newest `span` rows - the span, and the slots' ages as for the trend
+    window_periods: np.ndarray | None = None
+    window_periods_span: int | None = None
+    window_periods_age_rows: np.ndarray | None = None
     # Window quantile trend (rocmdash.ops.window_quantiles), when computed: per GPU
     # [N, S, P + 1, 4] - the three percentiles window_quantiles_pct and their count of each of
     # the trend's P + 1 column slots - and the slots' ages as for the trend
