@@ -1100,24 +1100,26 @@ PYBIND11_MODULE(_native, m) {
   m.def(
       "autocorr_ring",
       [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n, uint32_t span,
-         uintptr_t scale, uint32_t L, uintptr_t dst, uintptr_t stream) {
+         uintptr_t scale, uint32_t L, uintptr_t dst, uintptr_t stream, uint32_t share) {
         int e;
         {
           py::gil_scoped_release nogil;
           e = launch_autocorr_ring(reinterpret_cast<const float*>(base), stride, cols, depth, head, n, span,
                                    reinterpret_cast<const float*>(scale), L, reinterpret_cast<int64_t*>(dst),
-                                   reinterpret_cast<void*>(stream));
+                                   reinterpret_cast<void*>(stream), share);
         }
         if (e != 0) throw std::runtime_error("autocorr_ring failed: " + std::to_string(e));
       },
       py::arg("base_ptr"), py::arg("stride"), py::arg("cols"), py::arg("depth"), py::arg("head"), py::arg("n"),
-      py::arg("span"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
+      py::arg("span"), py::arg("scale_ptr"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"), py::arg("share") = 0,
       "Autocorrelation sums of every column of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) over "
-      "the newest min(n, span) rows of the window [head - n, head): scale [cols] floats -> dst [cols][lags + 1][4] int64.");
+      "the newest min(n, span) rows of the window [head - n, head): scale [cols] floats -> dst [cols][lags + 1][4] int64. "
+      "share 0: the launch rule decides; else chunks of 1024 rows per workgroup.");
   m.def(
       "xcorr_ring",
       [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n, uint32_t span,
-         uintptr_t scale, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uint32_t L, uintptr_t dst, uintptr_t stream) {
+         uintptr_t scale, const std::vector<std::pair<uint32_t, uint32_t>>& pairs, uint32_t L, uintptr_t dst, uintptr_t stream,
+         uint32_t share) {
         std::vector<uint32_t> flat;
         for (const auto& p : pairs) {
           flat.push_back(p.first);
@@ -1128,14 +1130,16 @@ PYBIND11_MODULE(_native, m) {
           py::gil_scoped_release nogil;
           e = launch_xcorr_ring(reinterpret_cast<const float*>(base), stride, cols, depth, head, n, span,
                                 reinterpret_cast<const float*>(scale), flat.data(), uint32_t(pairs.size()), L,
-                                reinterpret_cast<int64_t*>(dst), reinterpret_cast<void*>(stream));
+                                reinterpret_cast<int64_t*>(dst), reinterpret_cast<void*>(stream), share);
         }
         if (e != 0) throw std::runtime_error("xcorr_ring failed: " + std::to_string(e));
       },
       py::arg("base_ptr"), py::arg("stride"), py::arg("cols"), py::arg("depth"), py::arg("head"), py::arg("n"),
       py::arg("span"), py::arg("scale_ptr"), py::arg("pairs"), py::arg("lags"), py::arg("dst_ptr"), py::arg("stream"),
+      py::arg("share") = 0,
       "Cross-correlation sums of pairs [(a, b), ..] of columns of one time-major ring [depth][stride] (row r at slot r & (depth - 1)) "
-      "over the newest min(n, span) rows of the window [head - n, head): scale [cols] floats -> dst [K][2 lags + 1][6] int64.");
+      "over the newest min(n, span) rows of the window [head - n, head): scale [cols] floats -> dst [K][2 lags + 1][6] int64. "
+      "share 0: the launch rule decides; else chunks of 1024 rows per workgroup.");
   m.def(
       "joint_ring",
       [](uintptr_t base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n,

@@ -46,8 +46,8 @@ inline bool bad_autocorr(uint32_t span, const float* scale, uint32_t L, const in
 // [cols][L + 1][4] int64, 8-byte aligned, needs no initialisation. n == 0 or head == 0: all
 // zeroes. Returns a hipError_t: hipErrorInvalidValue, before any launch or write, unless span is
 // a power of two in [2^6, 2^20], 1 <= L <= 1024, launch_bucket_ring's ring conditions hold and
-// base / scale / dst are set.
+// base / scale / dst are set. share 0: the launch rule; else the chunks per workgroup, 1 <= share <= max(1, chunks).
 int launch_autocorr_ring(const float* base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n,
-                         uint32_t span, const float* scale, uint32_t L, int64_t* dst, void* stream);
+                         uint32_t span, const float* scale, uint32_t L, int64_t* dst, void* stream, uint32_t share = 0);
 
 }  // namespace rocmdash

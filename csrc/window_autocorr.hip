@@ -283,9 +283,10 @@ __global__ __launch_bounds__(kNT) void autocorr_ring_kernel(const AutocorrArgs a
 
 inline bool pow2(uint64_t x) { return x != 0 && (x & (x - 1)) == 0; }
 
-// the span [head - min(n, span), head) of one ring of `depth` rows onto dst (already zeroed)
+// the span [head - min(n, span), head) of one ring of `depth` rows onto dst (already zeroed);
+// share 0: the rule below, else the chunks of a workgroup, checked by the caller
 inline int run(const float* base, uint32_t stride, uint32_t cols, uint64_t depth, uint64_t head, uint64_t n, uint32_t span,
-               const float* scale, uint32_t L, int64_t* dst, hipStream_t stream) {
+               const float* scale, uint32_t L, int64_t* dst, hipStream_t stream, uint32_t share = 0) {
   const uint32_t N = uint32_t(std::min<uint64_t>(n, span));
   if (head == 0 || N == 0) return hipSuccess;  // the zeroes stand
   AutocorrArgs a{};
@@ -302,7 +303,7 @@ inline int run(const float* base, uint32_t stride, uint32_t cols, uint64_t depth
   // lags 0 .. L: L = 256 m - 1 fills its blocks; at L = 256 m the last block holds lag L alone
   const uint32_t groups = (cols + kG - 1) / kG, blocks = L / kLB + 1;
   const uint32_t shares = std::min(a.chunks, std::max(1u, kTargetGroups / (groups * blocks)));
-  a.share = (a.chunks + shares - 1) / shares;
+  a.share = share ? share : (a.chunks + shares - 1) / shares;
   hipLaunchKernelGGL(autocorr_ring_kernel, dim3((a.chunks + a.share - 1) / a.share, groups, blocks), dim3(kNT), 0, stream, a);
   return hipGetLastError();
 }
@@ -325,14 +326,15 @@ struct DeviceScope {  // the calling thread's device, restored on exit
 }  // namespace
 
 int launch_autocorr_ring(const float* base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n,
-                         uint32_t span, const float* scale, uint32_t L, int64_t* dst, void* stream_ptr) {
+                         uint32_t span, const float* scale, uint32_t L, int64_t* dst, void* stream_ptr, uint32_t share) {
   if (bad_autocorr(span, scale, L, dst) || base == nullptr || !pow2(depth) || n > depth || n > head || stride < 1 ||
       stride > kMaxAutocorrStride || cols < 1 || cols > stride)
     return hipErrorInvalidValue;
+  if (share > std::max(1u, (std::min(n, span) + kT - 1) / kT)) return hipErrorInvalidValue;  // 0: the rule
   auto stream = static_cast<hipStream_t>(stream_ptr);
   const hipError_t e = zero(dst, cols, L, stream);
   if (e != hipSuccess) return e;
-  return run(base, stride, cols, depth, head, n, span, scale, L, dst, stream);
+  return run(base, stride, cols, depth, head, n, span, scale, L, dst, stream, share);
 }
 
 // DeviceWindowSet::export_autocorr lives here with its kernel (device_window.h declares it); the

@@ -51,9 +51,9 @@ inline bool bad_xcorr(uint32_t span, const float* scale, const uint32_t* pairs, 
 // [K][2] columns of the ring, 1 <= K <= 8, both below cols and a != b. dst: device
 // [K][2L + 1][6] int64, 8-byte aligned, needs no initialisation. n == 0 or head == 0: all zeroes.
 // Returns a hipError_t: hipErrorInvalidValue, before any launch or write, unless
-// launch_autocorr_ring's conditions and these hold.
+// launch_autocorr_ring's conditions and these hold. share as launch_autocorr_ring: 0 is xcorr_share's rule.
 int launch_xcorr_ring(const float* base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n,
                       uint32_t span, const float* scale, const uint32_t* pairs, uint32_t K, uint32_t L, int64_t* dst,
-                      void* stream);
+                      void* stream, uint32_t share = 0);
 
 }  // namespace rocmdash

@@ -348,9 +348,10 @@ __global__ __launch_bounds__(kNT) void xcorr_ring_kernel(const XcorrArgs a) {
 
 inline bool pow2(uint64_t x) { return x != 0 && (x & (x - 1)) == 0; }
 
-// the pairs p of one ring of `depth` rows over its span [head - min(n, span), head) onto dst (already zeroed)
+// the pairs p of one ring of `depth` rows over its span [head - min(n, span), head) onto dst (already
+// zeroed); share 0: xcorr_share's rule, else the chunks of a workgroup, checked by the caller
 inline int run(const XcorrRingPairs& p, const float* base, uint32_t stride, uint64_t depth, uint64_t head, uint64_t n,
-               uint32_t span, const float* scale, uint32_t L, int64_t* dst, hipStream_t stream) {
+               uint32_t span, const float* scale, uint32_t L, int64_t* dst, hipStream_t stream, uint32_t share = 0) {
   const uint32_t N = uint32_t(std::min<uint64_t>(n, span));
   if (head == 0 || N == 0 || p.count == 0) return hipSuccess;  // the zeroes stand
   XcorrArgs a{};
@@ -370,7 +371,7 @@ inline int run(const XcorrRingPairs& p, const float* base, uint32_t stride, uint
     a.slot[i] = p.slot[i];
   }
   const uint32_t groups = xcorr_pair_groups(p.count), blocks = xcorr_lag_blocks(L);
-  a.share = xcorr_share(a.chunks, groups * blocks);
+  a.share = share ? share : xcorr_share(a.chunks, groups * blocks);
   hipLaunchKernelGGL(xcorr_ring_kernel, dim3(xcorr_share_groups(a.chunks, a.share), groups, blocks), dim3(kNT), 0, stream, a);
   return hipGetLastError();
 }
@@ -394,17 +395,18 @@ struct DeviceScope {  // the calling thread's device, restored on exit
 
 int launch_xcorr_ring(const float* base, uint32_t stride, uint32_t cols, uint32_t depth, uint64_t head, uint32_t n,
                       uint32_t span, const float* scale, const uint32_t* pairs, uint32_t K, uint32_t L, int64_t* dst,
-                      void* stream_ptr) {
+                      void* stream_ptr, uint32_t share) {
   if (bad_xcorr(span, scale, pairs, K, L, dst) || base == nullptr || !pow2(depth) || n > depth || n > head || stride < 1 ||
       stride > kMaxAutocorrStride || cols < 1 || cols > stride)
     return hipErrorInvalidValue;
+  if (share > std::max(1u, (std::min(n, span) + kT - 1) / kT)) return hipErrorInvalidValue;  // 0: the rule
   const XcorrRingSpan ring{0, cols};
   XcorrPlan plan;
   if (!xcorr_plan_pairs(pairs, K, &ring, 1, &plan)) return hipErrorInvalidValue;
   auto stream = static_cast<hipStream_t>(stream_ptr);
   const hipError_t e = zero(dst, K, L, stream);
   if (e != hipSuccess) return e;
-  return run(plan.rings[0], base, stride, depth, head, n, span, scale, L, dst, stream);
+  return run(plan.rings[0], base, stride, depth, head, n, span, scale, L, dst, stream, share);
 }
 
 // DeviceWindowSet::export_xcorr lives here with its kernel (device_window.h declares it); the

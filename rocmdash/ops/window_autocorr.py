@@ -219,14 +219,15 @@ def pick_period(acf, min_strength: float = MIN_STRENGTH, harmonic_tolerance: flo
     return None, None
 
 
-def window_autocorr(x, scale, L, span=None, head=None, window=None, out=None):
+def window_autocorr(x, scale, L, span=None, head=None, window=None, out=None, share=0):
     """Run the HIP kernel on a device tensor ``x`` ``[S, n]`` (float32, oldest first, NaN =
     invalid; one ring of S <= 64 series), being rows ``head - n .. head - 1`` (``head``
     defaults to n) of a window of ``window`` rows (default: the next power of two >= n), with
     ``scale`` ``[S]``, lags ``0 .. L`` and ``span`` (default 65536). The rows are laid into a
     time-major ring of depth ``2 * window`` at their slots, exactly like ``window_joint``, and
     ``autocorr_ring`` runs on the current stream. Returns int64 ``[S, L + 1, 4]`` on the device
-    (``out`` when given: a contiguous int64 device tensor of that shape, whatever it holds)."""
+    (``out`` when given: a contiguous int64 device tensor of that shape, whatever it holds).
+    ``share``: 0 for the launch rule, else the chunks of ``CHUNK`` rows a workgroup takes, ``1 .. max(1, chunks)``."""
     import torch
 
     from ..runtime.native import load
@@ -259,5 +260,5 @@ def window_autocorr(x, scale, L, span=None, head=None, window=None, out=None):
     elif out.dtype != torch.int64 or tuple(out.shape) != (S, L + 1, 4) or not out.is_contiguous() or out.device != x.device:
         raise ValueError(f"out must be a contiguous int64 [{S}, {L + 1}, 4] tensor on {x.device}")
     load().autocorr_ring(ring.data_ptr(), S, S, depth, head, n, span, sd.data_ptr(), L, out.data_ptr(),
-                         torch.cuda.current_stream(x.device).cuda_stream)
+                         torch.cuda.current_stream(x.device).cuda_stream, share=int(share))
     return out

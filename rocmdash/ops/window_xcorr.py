@@ -178,7 +178,7 @@ def pick_lag(ccf, min_strength: float = MIN_STRENGTH, tolerance: float = TOLERAN
     return k, float(ccf[L + k])
 
 
-def window_xcorr(x, pairs, scale, L, span=None, head=None, window=None, out=None):
+def window_xcorr(x, pairs, scale, L, span=None, head=None, window=None, out=None, share=0):
     """Run the HIP kernel on a device tensor ``x`` ``[S, n]`` (float32, oldest first, NaN =
     invalid; one ring of S <= 64 series), being rows ``head - n .. head - 1`` (``head``
     defaults to n) of a window of ``window`` rows (default: the next power of two >= n), with
@@ -186,7 +186,7 @@ def window_xcorr(x, pairs, scale, L, span=None, head=None, window=None, out=None
     laid into a time-major ring of depth ``2 * window`` at their slots, exactly like
     ``window_autocorr``, and ``xcorr_ring`` runs on the current stream. Returns int64 ``[K, 2L +
     1, 6]`` on the device (``out`` when given: a contiguous int64 device tensor of that shape,
-    whatever it holds)."""
+    whatever it holds). ``share``: 0 for the launch rule, else the chunks a workgroup takes, as ``window_autocorr``'s."""
     import torch
 
     from ..runtime.native import load
@@ -221,5 +221,5 @@ def window_xcorr(x, pairs, scale, L, span=None, head=None, window=None, out=None
     elif out.dtype != torch.int64 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != x.device:
         raise ValueError(f"out must be a contiguous int64 {list(shape)} tensor on {x.device}")
     load().xcorr_ring(ring.data_ptr(), S, S, depth, head, n, span, sd.data_ptr(), pairs, L, out.data_ptr(),
-                      torch.cuda.current_stream(x.device).cuda_stream)
+                      torch.cuda.current_stream(x.device).cuda_stream, share=int(share))
     return out

@@ -22,6 +22,7 @@ import numpy as np
 
 import _bucket_bounds
 import _exact
+import _window_xcorr
 
 PCT = (50.0, 90.0, 99.0)
 
@@ -150,6 +151,21 @@ def _assert_autocorr(got, x, scale, L, span=None, what=""):
         raise AssertionError(f"{what} n {x.shape[1]} L {L}: {np.count_nonzero(got != want)} words differ, first series {s} "
                              f"lag {k} word {j}: {got[s, k, j]} != {want[s, k, j]}")
     assert (want[:, 0, 1] == want[:, 0, 2]).all()
+    return want
+
+
+def _assert_periods(got, rows, scale, head, W, P, L, span, what=""):
+    """``got`` [S, P + 1, L + 1, 4] against the reference over ``rows`` [n, S] = rows head - n .. head - 1."""
+    from rocmdash.ops.window_periods import window_periods_reference
+
+    got = np.asarray(got)
+    want = window_periods_reference(rows, scale, head, W, P, L, span)
+    assert got.dtype == np.int64 and got.shape == want.shape, (got.shape, got.dtype, want.shape)
+    if not np.array_equal(got, want):
+        s, j, k, i = (int(v[0]) for v in np.nonzero(got != want))
+        raise AssertionError(f"{what} head {head} n {len(rows)} W {W} P {P} L {L} span {span}: "
+                             f"{np.count_nonzero(got != want)} words differ, first series {s} slot {j} lag {k} word {i}: "
+                             f"{got[s, j, k, i]} != {want[s, j, k, i]}")
     return want
 
 
@@ -429,6 +445,8 @@ def trace(sc):
 
 # ---- every export of a set against the references ---------------------------------------------
 P, B, L, K = 8, 16, 16, 2
+XCORR_CALL = 8  # pairs of one export_xcorr call (rocmdash.ops.window_joint.MAX_PAIRS)
+MIN_PERIODS_WINDOW = 512  # rocmdash.ops.window_periods.MIN_SPAN: a set of a shorter window refuses export_periods
 _BOUND_FAMILIES = tuple(_bucket_bounds.STATIC)
 
 
@@ -440,6 +458,21 @@ def export_bounds(S):
 def autocorr_span(W):
     """Half the window, so the span cuts it (the smallest span there is at W = 64)."""
     return max(64, W // 2)
+
+
+def periods_span(W):
+    """Half the window where the period trend takes it; from W = 1024 on the autocorrelation's span."""
+    return max(MIN_PERIODS_WINDOW, W // 2)
+
+
+def xcorr_pairs(firsts, widths):
+    """``(ring, (a, b))`` for every ring of two or more series, in REVERSED ring order: its first
+    series with its last for an even ring index, its last with its first for an odd one."""
+    out = []
+    for i, (f, w) in enumerate(zip(firsts, widths)):
+        if w >= 2:
+            out.append((i, (f, f + w - 1) if i % 2 == 0 else (f + w - 1, f)))
+    return out[::-1]
 
 
 class ExportBuffers:
@@ -461,6 +494,10 @@ class ExportBuffers:
         self.pairs = [(f, f + w - 1) for f, w in zip(self.firsts, widths) if w >= 2]
         self.pair_ring = [i for i, w in enumerate(widths) if w >= 2]
         self.pair_calls = [self.pairs[i:i + 8] for i in range(0, len(self.pairs), 8)]  # at most 8 pairs a call
+        # the cross-correlation's pairs: one per such ring too, but listed against the ring order
+        self.xpairs = xcorr_pairs(self.firsts, widths)
+        self.xpair_calls = [[p for _, p in self.xpairs[i:i + XCORR_CALL]] for i in range(0, len(self.xpairs), XCORR_CALL)]
+        self.periods_span = periods_span(W) if W >= MIN_PERIODS_WINDOW else None
         dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(cuda)  # noqa: E731
         self.bd, self.td, self.sd = dev(self.bounds), dev(self.thresholds), dev(self.scale)
         new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=cuda)  # noqa: E731
@@ -471,6 +508,8 @@ class ExportBuffers:
         self.quantiles = new((S, P + 1, 4), torch.float32)
         self.autocorr = new((S, L + 1, 4), torch.int64)
         self.excursions = new((S, K, 8), torch.int32)
+        self.xcorr = new((max(1, len(self.xpairs)), 2 * L + 1, 6), torch.int64)
+        self.periods = None if self.periods_span is None else new((S, P + 1, L + 1, 4), torch.int64)
         self.work_bytes = nat.excursion_workspace_bytes(S, K)
         self.work = new((self.work_bytes,), torch.uint8)
         self.sorted = None if long else new((S, 1 + W), torch.float32)
@@ -482,15 +521,17 @@ class ExportBuffers:
 
 def check_all_exports(ws, mirrors, W, bufs, out, what=""):
     """After a refresh of ``ws`` into ``out`` [S, 8]: every destination filled with -1, all
-    seven exports (and export_sorted of a DeviceWindowSet) enqueued, ONE synchronisation, then
+    nine exports (and export_sorted of a DeviceWindowSet) enqueued, ONE synchronisation, then
     each ring's slice of each output held to that feature's reference over the mirror's window,
-    and the cross-checks of the feature tests."""
+    and the cross-checks of the feature tests. export_xcorr takes one pair per ring of two or
+    more series, listed in reversed ring order in calls of at most 8 pairs (``xcorr_pairs``).
+    export_periods runs only where the set accepts it, W >= 512: the W = 64 scenarios skip it."""
     import torch
 
     b = bufs
     stream = torch.cuda.current_stream().cuda_stream
     dsts = [b.buckets, b.trend, b.heatmap, b.joint, b.quantiles, b.autocorr, b.excursions]
-    for d in dsts + ([] if b.long else [b.sorted]):
+    for d in dsts + [b.xcorr] + ([] if b.long else [b.sorted]) + ([] if b.periods is None else [b.periods]):
         d.fill_(-1)
     ws.export_buckets(b.bd.data_ptr(), B, b.buckets.data_ptr(), stream)
     ws.export_trend(P, b.trend.data_ptr(), stream)
@@ -502,9 +543,18 @@ def check_all_exports(ws, mirrors, W, bufs, out, what=""):
     ws.export_quantiles(P, b.quantiles.data_ptr(), stream, *PCT)
     ws.export_autocorr(b.span, b.sd.data_ptr(), L, b.autocorr.data_ptr(), stream)
     ws.export_excursions(b.td.data_ptr(), K, b.excursions.data_ptr(), b.work.data_ptr(), b.work_bytes, stream)
+    at = 0
+    for pairs in b.xpair_calls:
+        ws.export_xcorr(pairs, b.span, b.sd.data_ptr(), L, b.xcorr[at:].data_ptr(), stream)
+        at += len(pairs)
+    if b.periods is not None:
+        ws.export_periods(b.periods_span, P, b.sd.data_ptr(), L, b.periods.data_ptr(), stream)
     if not b.long:
         ws.export_sorted(b.sorted.data_ptr(), stream)
     torch.cuda.synchronize()
+    xcorr = b.xcorr.cpu().numpy()
+    periods = None if b.periods is None else b.periods.cpu().numpy()
+    xslot = {ring: k for k, (ring, _) in enumerate(b.xpairs)}
     buckets, trend, heatmap, joint, quantiles, autocorr, excursions = (d.cpu().numpy() for d in dsts)
     stats = out.cpu().numpy()
     sorted_ = None if b.long else b.sorted.cpu().numpy()
@@ -522,6 +572,15 @@ def check_all_exports(ws, mirrors, W, bufs, out, what=""):
         if i in b.pair_ring:
             k = b.pair_ring.index(i)
             _assert_joint(joint[k:k + 1], rows, [(0, w - 1)], b.bounds[sl], what=f"{at} joint")
+        if i in xslot:
+            k = xslot[i]
+            pa, pb = b.xpairs[k][1]
+            _window_xcorr.assert_xcorr(xcorr[k:k + 1], rows.T, [(pa - f, pb - f)], b.scale[sl], L, b.span,
+                                       what=f"{at} xcorr slot {k} pair ({pa}, {pb})")
+            if head == 0:
+                assert not xcorr[k].any(), f"{at} xcorr slot {k}: a ring without rows"
+        if periods is not None:
+            _assert_periods(periods[sl], rows, b.scale[sl], head, W, P, L, b.periods_span, what=f"{at} periods")
         if sorted_ is not None:
             _assert_sorted(sorted_[sl], rows, W, what=f"{at} sorted")
     # the exports against each other and against the statistics of the same refresh
@@ -531,3 +590,6 @@ def check_all_exports(ws, mirrors, W, bufs, out, what=""):
     np.testing.assert_array_equal(trend[:, :, 3].sum(axis=1), stats[:, _exact.COUNT], err_msg=f"{what}: trend counts / count")
     np.testing.assert_array_equal(quantiles[:, :, 3], trend[:, :, 3], err_msg=f"{what}: quantile counts / trend counts")
     np.testing.assert_array_equal(excursions[:, 0, 1], stats[:, _exact.COUNT], err_msg=f"{what}: excursions' valid / count")
+    if periods is not None and b.periods_span == b.span:  # the slots cut the autocorrelation's rows: lag 0 adds up
+        np.testing.assert_array_equal(periods[:, :, 0, 0].sum(axis=1), autocorr[:, 0, 0], err_msg=f"{what}: periods' n_0 / autocorr")
+        np.testing.assert_array_equal(periods[:, :, 0, 3].sum(axis=1), autocorr[:, 0, 3], err_msg=f"{what}: periods' Sxy_0 / autocorr")

@@ -1,7 +1,7 @@
 """Every window export over the ring states its own test never reaches: one test per scenario of
 tests/_window_exports.py. After EVERY refresh of the scenario ``check_all_exports`` holds all
-seven exports (and a DeviceWindowSet's sorted windows) of every ring to the CPU references over
-a host mirror - several rings at different heads, a ring without rows beside a full one, widths
+nine exports - export_periods only where the set accepts it, W >= 512 - (and a DeviceWindowSet's
+sorted windows) of every ring to the CPU references over a host mirror - several rings at different heads, a ring without rows beside a full one, widths
 that take two segments or never get inline rows, lost rows (the 0xFF fill: negative NaNs with a
 full payload), unpinned and staged sets, a captured graph, two launches of the exports that
 batch by eight rings. The set's own counters are held to the schedule's trace
