@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "device_scope.h"
 #include "long_window.h"
 #include "window_buckets.h"
 
@@ -142,7 +143,6 @@ __global__ __launch_bounds__(kFinalizeNT) void bucket_finalize_kernel(double* ds
   if (lane <= B) *slot = double(c);
 }
 
-inline bool pow2(uint64_t x) { return x != 0 && (x & (x - 1)) == 0; }
 inline bool bad_buckets(const float* bounds, uint32_t B, const double* dst) {
   return B < 1 || B > kMaxBuckets || bounds == nullptr || dst == nullptr || (reinterpret_cast<uintptr_t>(dst) & 7u) != 0;
 }
@@ -182,17 +182,6 @@ struct BucketLaunches {
     hipLaunchKernelGGL(bucket_finalize_kernel, dim3((S + kFinalizeNT / 64 - 1) / (kFinalizeNT / 64)), dim3(kFinalizeNT),
                        0, stream, dst, S, a.B);
     return hipGetLastError();
-  }
-};
-
-struct DeviceScope {  // the calling thread's device, restored on exit
-  int prev = -1, dev;
-  explicit DeviceScope(int d) : dev(d) {
-    (void)hipGetDevice(&prev);
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceScope() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
   }
 };
 

@@ -6,26 +6,21 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "device_scope.h"
 #include "device_window.h"
 #include "long_window.h"
+#include "window_lag_dev.h"
 
 namespace rocmdash {
 namespace {
 
-constexpr int kNT = 256;                 // 4 waves; 184 VGPRs: 2 waves per SIMD, two workgroups share a CU
-constexpr uint32_t kT = kAutocorrChunk;  // rows of a chunk
-constexpr uint32_t kKT = 8;              // consecutive lags a thread owns: one 16-byte LDS read
-constexpr uint32_t kG = 8;               // series of a workgroup
-constexpr uint32_t kLB = 256;             // lags of a workgroup: every thread owns one (series, 8 lags)
-constexpr uint32_t kPitch = kT + kMaxAutocorrLags + 16;  // words of a series: chunk, halo, the last read's reach
-constexpr uint32_t kBlocks = kPitch / 8;                 // 8-word blocks of a series
-constexpr uint32_t kPBPitch = kBlocks + 2;
-constexpr uint32_t kPerLane = (kBlocks + 63) / 64;  // blocks a lane sums in the prefix scan
-constexpr uint32_t kFold = 128;                     // rows an int32 partial takes: 128 x 4095^2 < 2^31
-constexpr uint32_t kInvalid = 0x8000u;              // bit 15 of a word: no sample (NaN, or past the span)
-constexpr uint32_t kTargetGroups = 1024;            // workgroups of a launch: two rounds of 2 per CU
-static_assert(kPitch % 8 == 0 && (kPitch * 2) % 16 == 0 && kLB % kKT == 0 && kT % 16 == 0, "16-byte LDS reads");
-static_assert(kG * (kLB / kKT) == kNT, "one item per thread");
+using namespace lag;
+
+constexpr int kNT = int(kThreads);  // 184 VGPRs: 2 waves per SIMD, two workgroups share a CU
+constexpr uint32_t kG = 8;          // series of a workgroup
+constexpr uint32_t kLB = 256;       // lags of a workgroup: every thread owns one (series, 8 lags)
+constexpr uint32_t kTargetGroups = 1024;  // workgroups of a launch: two rounds of 2 per CU
+static_assert(kG == kRows && kLB % kKT == 0 && kG * (kLB / kKT) == kNT, "one item per thread");
 
 struct AutocorrArgs {
   const float* base;        // the ring's first float
@@ -34,126 +29,6 @@ struct AutocorrArgs {
   uint64_t first;           // the span's oldest row: head - N
   uint32_t stride, cols, mask, N, L, chunks, share;  // mask: depth - 1; share: chunks of a workgroup
 };
-
-__device__ inline uint32_t lo12(uint32_t w) { return w & 0xfffu; }
-__device__ inline uint32_t hi12(uint32_t w) { return (w >> 16) & 0xfffu; }
-
-// a x b + c, a and b below 2^24: one full-rate instruction, and stated as one. Written as
-// a * b + c or with __umul24, ROCm 7.2.0 (AMD clang 22.0.0git, roc-7.2.0) combines the chains of
-// products of 12-bit fields into v_dot4_u32_u8, which keeps 8 bits of each factor: the sums of
-// lags 1 - 3 and 5 - 7 of every 8 are short for q above 255. Plain C++ can return once a
-// compiler no longer does that; tests/test_gpu_window_autocorr.py would show it.
-__device__ inline uint32_t mad24(uint32_t a, uint32_t b, uint32_t c) {
-  uint32_t d;
-  asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-
-// the q of 8 consecutive words
-__device__ inline void unpack_q(const uint4 p, uint32_t (&q)[8]) {
-  const uint32_t w[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    q[2 * i] = lo12(w[i]);
-    q[2 * i + 1] = hi12(w[i]);
-  }
-}
-
-// their validity: 1 for a sample, 0 for none
-__device__ inline void unpack_v(const uint4 p, uint32_t (&v)[8]) {
-  const uint32_t w[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = (~w[i] >> 15) & 1u;
-    v[2 * i + 1] = ~w[i] >> 31;
-  }
-}
-
-// What a walk over the chunk sums. kXY: Sxy alone - all a clean series needs from the loop.
-// kXYandY: Sxy and Sy, kNandX: n and Sx - the two walks of a series with an invalid sample, two
-// so that either stays within the registers of the first.
-enum Walk { kXY, kXYandY, kNandX };
-
-// the x side of 8 rows: x1 multiplies into p1, x2 (kXYandY only) into p2
-template <Walk kW>
-__device__ inline void unpack_x(const uint4 p, uint32_t (&x1)[8], uint32_t (&x2)[8]) {
-  unpack_q(p, x1);
-  if (kW == kXYandY) unpack_v(p, x2);
-  if (kW == kNandX) {  // n in bits 0-7 (at most 128 per fold), Sx in bits 8-31 (at most 128 x 4095)
-    unpack_v(p, x2);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) x1[i] = x2[i] | (x1[i] << 8);
-  }
-}
-
-template <Walk kW>
-__device__ inline void unpack_y(const uint4 p, uint32_t (&y)[8]) {
-  if (kW == kNandX)
-    unpack_v(p, y);
-  else
-    unpack_q(p, y);
-}
-
-// 8 rows x 8 lags: x = rows t .. t + 7, (ya, yb) = rows t + k0 .. t + k0 + 15; every factor is below 2^24
-template <Walk kW>
-__device__ inline void mac(const uint32_t (&x1)[8], const uint32_t (&x2)[8], const uint32_t (&ya)[8], const uint32_t (&yb)[8],
-                           uint32_t (&p1)[kKT], uint32_t (&p2)[kKT]) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-#pragma unroll
-    for (int j = 0; j < int(kKT); ++j) {
-      const int e = i + j;
-      const uint32_t y = e < 8 ? ya[e & 7] : yb[e & 7];
-      p1[j] = mad24(x1[i], y, p1[j]);
-      if (kW == kXYandY) p2[j] = mad24(x2[i], y, p2[j]);
-    }
-  }
-}
-
-// One thread's chunk: lags k0 .. k0 + 7 of the series at ws over rows [0, tend), tend a multiple
-// of 16. Words past the span are invalid with q = 0, so no row needs a bound. kXY and kXYandY add
-// to (s1, s2) = (Sxy, Sy), kNandX to (n, Sx).
-template <Walk kW>
-__device__ inline void tile(const uint16_t* ws, uint32_t k0, uint32_t tend, uint64_t (&s1)[kKT], uint64_t (&s2)[kKT]) {
-  const uint4* const xr = reinterpret_cast<const uint4*>(ws);
-  const uint4* const yr = reinterpret_cast<const uint4*>(ws + k0);
-  uint32_t ya[8], yb[8], x1[8], x2[8];
-  unpack_y<kW>(yr[0], ya);
-#pragma unroll 1
-  for (uint32_t t = 0; t < tend; t += kFold) {
-    uint32_t p1[kKT] = {}, p2[kKT] = {};
-    const uint32_t ue = min(t + kFold, tend) >> 3;
-#pragma unroll 1
-    for (uint32_t u = t >> 3; u < ue; u += 2) {  // the window of 16 y slides by 8: (a, b) then (b, a)
-      unpack_x<kW>(xr[u], x1, x2);
-      unpack_y<kW>(yr[u + 1], yb);
-      mac<kW>(x1, x2, ya, yb, p1, p2);
-      unpack_x<kW>(xr[u + 1], x1, x2);
-      unpack_y<kW>(yr[u + 2], ya);
-      mac<kW>(x1, x2, yb, ya, p1, p2);
-    }
-#pragma unroll
-    for (int j = 0; j < int(kKT); ++j) {
-      if (kW == kNandX) {
-        s1[j] += p1[j] & 0xffu;
-        s2[j] += p1[j] >> 8;
-      } else {
-        s1[j] += p1[j];
-        if (kW == kXYandY) s2[j] += p2[j];
-      }
-    }
-  }
-}
-
-// sum of q over words [0, e) of a series: its block prefix and the first e % 8 words of the block
-__device__ inline uint32_t prefix(const uint16_t* ws, const uint32_t* pbs, uint32_t e) {
-  uint32_t q[8];
-  unpack_q(reinterpret_cast<const uint4*>(ws)[e >> 3], q);
-  uint32_t r = pbs[e >> 3];
-#pragma unroll
-  for (uint32_t i = 0; i < 7; ++i) r += i < (e & 7u) ? q[i] : 0u;
-  return r;
-}
 
 // grid (shares of chunks, groups of kG series, blocks of kLB lags). Per chunk: (1) the rows
 // [t0, t0 + len) of the span - the chunk and the halo this block's lags reach - are read with
@@ -281,8 +156,6 @@ __global__ __launch_bounds__(kNT) void autocorr_ring_kernel(const AutocorrArgs a
   }
 }
 
-inline bool pow2(uint64_t x) { return x != 0 && (x & (x - 1)) == 0; }
-
 // the span [head - min(n, span), head) of one ring of `depth` rows onto dst (already zeroed);
 // share 0: the rule below, else the chunks of a workgroup, checked by the caller
 inline int run(const float* base, uint32_t stride, uint32_t cols, uint64_t depth, uint64_t head, uint64_t n, uint32_t span,
@@ -311,17 +184,6 @@ inline int run(const float* base, uint32_t stride, uint32_t cols, uint64_t depth
 inline hipError_t zero(int64_t* dst, uint32_t S, uint32_t L, hipStream_t stream) {
   return hipMemsetAsync(dst, 0, size_t(S) * (L + 1) * 4 * sizeof(int64_t), stream);
 }
-
-struct DeviceScope {  // the calling thread's device, restored on exit
-  int prev = -1, dev;
-  explicit DeviceScope(int d) : dev(d) {
-    (void)hipGetDevice(&prev);
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceScope() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-  }
-};
 
 }  // namespace
 

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "device_scope.h"
 #include "device_window.h"
 #include "long_window.h"
 #include "window_excursions_monoid.h"
@@ -171,7 +172,6 @@ __global__ __launch_bounds__(kFinalizeNT) void excursion_finalize_kernel(const E
   }
 }
 
-inline bool pow2(uint64_t x) { return x != 0 && (x & (x - 1)) == 0; }
 inline bool misaligned(const void* p, uintptr_t a) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 inline bool bad_buffers(const float* thr, uint32_t K, const int32_t* dst, const void* work, size_t work_bytes,
                         uint32_t series) {
@@ -223,17 +223,6 @@ struct ExcLaunches {
   int finish() {
     flush();
     return hipGetLastError();
-  }
-};
-
-struct DeviceScope {  // the calling thread's device, restored on exit
-  int prev = -1, dev;
-  explicit DeviceScope(int d) : dev(d) {
-    (void)hipGetDevice(&prev);
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceScope() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
   }
 };
 

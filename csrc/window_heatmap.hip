@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "device_scope.h"
 #include "device_window.h"
 #include "long_window.h"
 #include "window_buckets.h"
@@ -155,7 +156,6 @@ __global__ __launch_bounds__(NT) void heatmap_kernel(const HeatArgs a) {
   heat_slot<NT / 64>(a.r[blockIdx.y], a.log2c, a.P, a.B, blockIdx.x, sb, cnt);
 }
 
-inline bool pow2(uint64_t x) { return x != 0 && (x & (x - 1)) == 0; }
 inline uint32_t log2u(uint32_t x) { return 31u - uint32_t(__builtin_clz(x)); }
 inline bool bad_columns(uint32_t P) { return P < kMinTrendColumns || P > kMaxTrendColumns || !pow2(P); }
 inline bool bad_buckets(const float* bounds, uint32_t B, const int32_t* dst) {
@@ -171,17 +171,6 @@ void launch(const HeatArgs& a, uint32_t n, hipStream_t stream) {
   else
     hipLaunchKernelGGL(heatmap_kernel<kGroupNT>, dim3(a.P + 1, n), dim3(kGroupNT), 0, stream, a);
 }
-
-struct DeviceScope {  // the calling thread's device, restored on exit
-  int prev = -1, dev;
-  explicit DeviceScope(int d) : dev(d) {
-    (void)hipGetDevice(&prev);
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceScope() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-  }
-};
 
 // One export over a set's rings: ring(i, &R) fills base / stride / cols / mask / head / n and
 // returns the ring's first series.

@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "device_scope.h"
 #include "device_window.h"
 #include "long_window.h"
 
@@ -158,7 +159,6 @@ __global__ __launch_bounds__(kNT) void joint_ring_kernel(const JointArgs a) {
   }
 }
 
-inline bool pow2(uint64_t x) { return x != 0 && (x & (x - 1)) == 0; }
 inline bool bad_joint(uint32_t K, const float* bounds, uint32_t B, const int32_t* dst) {
   return K < 1 || K > kMaxJointPairs || B < 1 || B > kMaxJointBuckets || bounds == nullptr || dst == nullptr ||
          (reinterpret_cast<uintptr_t>(dst) & 3u) != 0;
@@ -189,17 +189,6 @@ struct JointLaunch {
 inline hipError_t zero(int32_t* dst, uint32_t K, uint32_t B, hipStream_t stream) {
   return hipMemsetAsync(dst, 0, size_t(K) * (B + 1) * (B + 1) * sizeof(int32_t), stream);
 }
-
-struct DeviceScope {  // the calling thread's device, restored on exit
-  int prev = -1, dev;
-  explicit DeviceScope(int d) : dev(d) {
-    (void)hipGetDevice(&prev);
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceScope() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-  }
-};
 
 }  // namespace
 

@@ -1,20 +1,41 @@
-// Word-level device routines of the lag walk: a series of a chunk sits in LDS as 16-bit words
-// [chunk + halo] (q in bits 0-11, bit 15 = no sample); a thread owns 8 consecutive lags and walks
-// the chunk 8 rows at a time. These are the routines window_autocorr.hip and window_xcorr.hip each
-// carry a copy of; only window_periods.hip includes this header. Moving those two onto it changes
-// how tested code is built, so it is a follow-up of its own and not done here.
+// The lag walk of window_autocorr.hip, window_xcorr.hip and window_periods.hip. A workgroup of
+// kThreads keeps kRows series of a chunk in LDS as 16-bit words [chunk + halo] (q in bits 0-11,
+// bit 15 = no sample); a thread owns 8 consecutive lags of one row (against itself, or against a
+// second row) and walks the chunk 8 rows at a time. Here, once: the LDS geometry, the word-level
+// routines, the walk set with its unpack and its 8 x 8 mac, and the one-series tile and prefix.
+// Each kernel keeps its own chunk loader, block prefix scan and per-thread step, and
+// window_xcorr.hip its two-row tile over Sums: written as functions of this header (one tile over
+// an accumulator type, a load and a scan stage), the same statements compile to other
+// instruction streams for all three kernels under ROCm 7.2.0 - the one-series step as a function
+// takes 188 VGPRs for 184 - and the one-series kernels then ran 0.4 - 0.8 % outside their parent's
+// run-to-run spread on rows with NaN (profiles/lag_shared/). As it stands every kernel compiles
+// to the instruction stream it had with its private copy.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "window_autocorr.h"
+#include "window_xcorr_plan.h"  // for the static_assert on the geometry below, nothing else
+
 namespace rocmdash {
 namespace lag {
 
+constexpr uint32_t kThreads = 256;     // 4 waves; under 256 VGPRs two waves share a SIMD, two workgroups a CU
+constexpr uint32_t kRows = 8;          // LDS rows of a workgroup: one loader lane of every 8 each
+constexpr uint32_t kT = kAutocorrChunk;  // rows of a chunk
 constexpr uint32_t kKT = 8;            // consecutive lags a thread owns: one 16-byte LDS read
 constexpr uint32_t kFold = 128;        // rows an int32 partial takes: 128 x 4095^2 < 2^31
 constexpr uint32_t kInvalid = 0x8000u;  // bit 15 of a word: no sample (NaN, or past the rows' end)
+constexpr uint32_t kPitch = kT + kMaxAutocorrLags + 16;  // words of an LDS row: chunk, halo, the last read's reach
+constexpr uint32_t kBlocks = kPitch / 8;                 // 8-word blocks of a row
+constexpr uint32_t kPBPitch = kBlocks + 2;
+constexpr uint32_t kPerLane = (kBlocks + 63) / 64;  // blocks a lane sums in the prefix scan
+static_assert(kPitch % 8 == 0 && (kPitch * 2) % 16 == 0 && kT % 16 == 0, "16-byte LDS reads");
+static_assert(kPitch == kXcorrPitch && kThreads == kXcorrThreads && kKT == kXcorrLagTile,
+              "the geometry window_xcorr_plan.h plans with on the host");
+static_assert(uint64_t(kFold) * kAutocorrQMax * kAutocorrQMax < (1ull << 31), "an int32 partial, of q^2 x v too");
 
 __device__ inline uint32_t lo12(uint32_t w) { return w & 0xfffu; }
 __device__ inline uint32_t hi12(uint32_t w) { return (w >> 16) & 0xfffu; }
@@ -23,7 +44,8 @@ __device__ inline uint32_t hi12(uint32_t w) { return (w >> 16) & 0xfffu; }
 // a * b + c or with __umul24, ROCm 7.2.0 (AMD clang 22.0.0git, roc-7.2.0) combines the chains of
 // products of 12-bit fields into v_dot4_u32_u8, which keeps 8 bits of each factor: the sums of
 // lags 1 - 3 and 5 - 7 of every 8 are short for q above 255. Plain C++ can return once a
-// compiler no longer does that; tests/test_gpu_window_periods.py would show it.
+// compiler no longer does that; tests/test_gpu_window_autocorr.py, test_gpu_window_xcorr.py and
+// test_gpu_window_periods.py would each show it.
 __device__ inline uint32_t mad24(uint32_t a, uint32_t b, uint32_t c) {
   uint32_t d;
   asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
@@ -50,27 +72,47 @@ __device__ inline void unpack_v(const uint4 p, uint32_t (&v)[8]) {
   }
 }
 
-// What a walk over the chunk sums. kXY: Sxy alone - all a clean series needs from the loop.
-// kXYandY: Sxy and Sy, kNandX: n and Sx - the two walks of a series with an invalid sample, two
-// so that either stays within the registers of the first.
-enum Walk { kXY, kXYandY, kNandX };
+// their q^2: below 2^24, so still a factor of mad24
+__device__ inline void unpack_qq(const uint4 p, uint32_t (&s)[8]) {
+  unpack_q(p, s);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s[i] = mad24(s[i], s[i], 0u);
+}
 
-// the x side of 8 rows: x1 multiplies into p1, x2 (kXYandY only) into p2
+// What a walk over the chunk sums, as (p1, p2). kXY: (Sxy, -) - all a clean item needs from the
+// loop. A marked series walks twice, kXYandY: (Sxy, Sy) and kNandX: (n | Sx << 8, -); a marked
+// pair three times, kXYandY, kNXandXX: (n | Sx << 8, Sxx) and kYY: (Syy, -) - several walks so
+// that each stays within the registers of kXYandY.
+enum Walk { kXY, kXYandY, kNandX, kNXandXX, kYY };
+
+// the x side of 8 rows: x1 multiplies into p1, x2 (kXYandY, kNXandXX) into p2
 template <Walk kW>
 __device__ inline void unpack_x(const uint4 p, uint32_t (&x1)[8], uint32_t (&x2)[8]) {
-  unpack_q(p, x1);
+  if (kW == kYY) unpack_v(p, x1);
+  if (kW != kYY) unpack_q(p, x1);
   if (kW == kXYandY) unpack_v(p, x2);
   if (kW == kNandX) {  // n in bits 0-7 (at most 128 per fold), Sx in bits 8-31 (at most 128 x 4095)
     unpack_v(p, x2);
 #pragma unroll
     for (int i = 0; i < 8; ++i) x1[i] = x2[i] | (x1[i] << 8);
   }
+  if (kW == kNXandXX) {  // p1 as kNandX, p2 from q^2
+    uint32_t v[8];
+    unpack_v(p, v);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      x2[i] = mad24(x1[i], x1[i], 0u);
+      x1[i] = v[i] | (x1[i] << 8);
+    }
+  }
 }
 
 template <Walk kW>
 __device__ inline void unpack_y(const uint4 p, uint32_t (&y)[8]) {
-  if (kW == kNandX)
+  if (kW == kNandX || kW == kNXandXX)
     unpack_v(p, y);
+  else if (kW == kYY)
+    unpack_qq(p, y);
   else
     unpack_q(p, y);
 }
@@ -86,7 +128,7 @@ __device__ inline void mac(const uint32_t (&x1)[8], const uint32_t (&x2)[8], con
       const int e = i + j;
       const uint32_t y = e < 8 ? ya[e & 7] : yb[e & 7];
       p1[j] = mad24(x1[i], y, p1[j]);
-      if (kW == kXYandY) p2[j] = mad24(x2[i], y, p2[j]);
+      if (kW == kXYandY || kW == kNXandXX) p2[j] = mad24(x2[i], y, p2[j]);
     }
   }
 }
@@ -126,7 +168,7 @@ __device__ inline void tile(const uint16_t* ws, uint32_t k0, uint32_t tend, uint
   }
 }
 
-// sum of q over words [0, e) of a series: its block prefix and the first e % 8 words of the block
+// sum of q over words [0, e) of a row: its block prefix and the first e % 8 words of the block
 __device__ inline uint32_t prefix(const uint16_t* ws, const uint32_t* pbs, uint32_t e) {
   uint32_t q[8];
   unpack_q(reinterpret_cast<const uint4*>(ws)[e >> 3], q);

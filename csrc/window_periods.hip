@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdint>
 
+#include "device_scope.h"
 #include "device_window.h"
 #include "long_window.h"
 #include "window_lag_dev.h"
@@ -16,17 +17,11 @@ namespace {
 
 using namespace lag;
 
-constexpr int kNT = 256;                // 4 waves; 2 waves per SIMD, two workgroups share a CU
-constexpr uint32_t kT = kPeriodsChunk;  // rows of a chunk
+constexpr int kNT = int(kThreads);  // 2 waves per SIMD, two workgroups share a CU
 constexpr uint32_t kG = kPeriodsSeriesGroup;
 constexpr uint32_t kLB = kPeriodsLagBlock;  // every thread owns one (series, 8 lags)
-constexpr uint32_t kPitch = kT + kMaxAutocorrLags + 16;  // words of a series: chunk, halo, the last read's reach
-constexpr uint32_t kBlocks = kPitch / 8;                 // 8-word blocks of a series
-constexpr uint32_t kPBPitch = kBlocks + 2;
-constexpr uint32_t kPerLane = (kBlocks + 63) / 64;  // blocks a lane sums in the prefix scan
-static_assert(kT == kAutocorrChunk, "the autocorrelation's chunk");
-static_assert(kPitch % 8 == 0 && (kPitch * 2) % 16 == 0 && kLB % kKT == 0 && kT % 16 == 0, "16-byte LDS reads");
-static_assert(kG * (kLB / kKT) == kNT, "one item per thread");
+static_assert(kPeriodsChunk == kT, "the autocorrelation's chunk");
+static_assert(kG == kRows && kLB % kKT == 0 && kG * (kLB / kKT) == kNT, "one item per thread");
 
 struct PeriodsArgs {
   const float* base;        // the ring's first float
@@ -204,17 +199,6 @@ inline int run(const float* base, uint32_t stride, uint32_t cols, uint64_t depth
   }
   return hipGetLastError();
 }
-
-struct DeviceScope {  // the calling thread's device, restored on exit
-  int prev = -1, dev;
-  explicit DeviceScope(int d) : dev(d) {
-    (void)hipGetDevice(&prev);
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceScope() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-  }
-};
 
 }  // namespace
 

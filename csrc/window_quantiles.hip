@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "device_scope.h"
 #include "device_window.h"
 #include "long_window.h"
 #include "long_window_dev.h"
@@ -337,7 +338,6 @@ __global__ __launch_bounds__(kSelectNT) void quant_select_kernel(const QuantArgs
   }
 }
 
-inline bool pow2(uint64_t x) { return x != 0 && (x & (x - 1)) == 0; }
 inline uint32_t log2u(uint32_t x) { return 31u - uint32_t(__builtin_clz(x)); }
 inline bool bad_columns(uint32_t P) { return P < kMinTrendColumns || P > kMaxTrendColumns || !pow2(P); }
 inline bool bad_dst(const float* dst) { return dst == nullptr || (reinterpret_cast<uintptr_t>(dst) & 15u) != 0; }
@@ -375,17 +375,6 @@ void launch(const QuantArgs& a0, uint32_t n, hipStream_t stream) {
   else
     hipLaunchKernelGGL((quant_sort_kernel<16, kSortKeys16>), grid, dim3(1024), 0, stream, a);
 }
-
-struct DeviceScope {  // the calling thread's device, restored on exit
-  int prev = -1, dev;
-  explicit DeviceScope(int d) : dev(d) {
-    (void)hipGetDevice(&prev);
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceScope() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-  }
-};
 
 // One export over a set's rings: ring(i, &R) fills base / stride / cols / mask / head / n and
 // returns the ring's first series.

@@ -7,26 +7,20 @@
 #include <cstdint>
 #include <vector>
 
+#include "device_scope.h"
 #include "device_window.h"
 #include "long_window.h"
+#include "window_lag_dev.h"
 
 namespace rocmdash {
 namespace {
 
-constexpr int kNT = int(kXcorrThreads);  // 4 waves; 2 waves per SIMD, two workgroups share a CU
-constexpr uint32_t kT = kAutocorrChunk;  // rows of a chunk
-constexpr uint32_t kKT = kXcorrLagTile;  // consecutive lags a thread owns: one 16-byte LDS read
+using namespace lag;
+
+constexpr int kNT = int(kThreads);  // 220 VGPRs: 2 waves per SIMD, two workgroups share a CU
 constexpr uint32_t kR = 2 * kXcorrGroupPairs;  // LDS rows, and directed items, of a workgroup
 constexpr uint32_t kLB = kXcorrLagBlock;
-constexpr uint32_t kPitch = kXcorrPitch;                 // words of a row: chunk, halo, the last read's reach
-constexpr uint32_t kBlocks = kPitch / 8;                 // 8-word blocks of a row
-constexpr uint32_t kPBPitch = kBlocks + 2;
-constexpr uint32_t kPerLane = (kBlocks + 63) / 64;  // blocks a lane sums in the prefix scan
-constexpr uint32_t kFold = 128;                     // rows an int32 partial takes: 128 x 4095^2 < 2^31
-constexpr uint32_t kInvalid = 0x8000u;              // bit 15 of a word: no sample (NaN, or past the span)
-static_assert(kPitch % 8 == 0 && (kPitch * 2) % 16 == 0 && kLB % kKT == 0 && kT % 16 == 0, "16-byte LDS reads");
-static_assert(kR * (kLB / kKT) == kNT && kR == 8, "one item per thread, one loader column per row");
-static_assert(uint64_t(kFold) * kAutocorrQMax * kAutocorrQMax < (1ull << 31), "an int32 partial of q^2 x v");
+static_assert(kLB % kKT == 0 && kR * (kLB / kKT) == kNT && kR == kRows, "one item per thread, one loader column per row");
 
 struct XcorrArgs {
   const float* base;        // the ring's first float
@@ -37,95 +31,6 @@ struct XcorrArgs {
   uint8_t col[2 * kMaxXcorrPairs];                    // row 2i: pair i's a, row 2i + 1: its b
   uint8_t slot[kMaxXcorrPairs];                       // pair i's k of dst
 };
-
-__device__ inline uint32_t lo12(uint32_t w) { return w & 0xfffu; }
-__device__ inline uint32_t hi12(uint32_t w) { return (w >> 16) & 0xfffu; }
-
-// a x b + c, a and b below 2^24: one full-rate instruction, and stated as one, as in
-// window_autocorr.hip and for its reason: written as a * b + c or with __umul24, ROCm 7.2.0
-// combines the chains of products of 12-bit fields into v_dot4_u32_u8, which keeps 8 bits of
-// each factor. tests/test_gpu_window_xcorr.py would show it.
-__device__ inline uint32_t mad24(uint32_t a, uint32_t b, uint32_t c) {
-  uint32_t d;
-  asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-
-// the q of 8 consecutive words
-__device__ inline void unpack_q(const uint4 p, uint32_t (&q)[8]) {
-  const uint32_t w[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    q[2 * i] = lo12(w[i]);
-    q[2 * i + 1] = hi12(w[i]);
-  }
-}
-
-// their validity: 1 for a sample, 0 for none
-__device__ inline void unpack_v(const uint4 p, uint32_t (&v)[8]) {
-  const uint32_t w[4] = {p.x, p.y, p.z, p.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = (~w[i] >> 15) & 1u;
-    v[2 * i + 1] = ~w[i] >> 31;
-  }
-}
-
-// their q^2: below 2^24, so still a factor of mad24
-__device__ inline void unpack_qq(const uint4 p, uint32_t (&s)[8]) {
-  unpack_q(p, s);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) s[i] = mad24(s[i], s[i], 0u);
-}
-
-// What a walk over the chunk sums. kXY: Sxy alone - all a clean item needs from the loop. The
-// three walks of an item with an invalid sample: kXYandY (Sxy, Sy: y = q), kNXandXX (n, Sx, Sxx:
-// y = v) and kYY (Syy: y = q^2) - three so that each stays within the registers of kXYandY.
-enum Walk { kXY, kXYandY, kNXandXX, kYY };
-
-// the x side of 8 rows: x1 multiplies into p1, x2 (kXYandY, kNXandXX) into p2
-template <Walk kW>
-__device__ inline void unpack_x(const uint4 p, uint32_t (&x1)[8], uint32_t (&x2)[8]) {
-  if (kW == kXY || kW == kXYandY) unpack_q(p, x1);
-  if (kW == kXYandY) unpack_v(p, x2);
-  if (kW == kYY) unpack_v(p, x1);
-  if (kW == kNXandXX) {  // p1: n in bits 0-7 (at most 128 per fold), Sx in bits 8-31 (at most 128 x 4095)
-    uint32_t v[8];
-    unpack_q(p, x1);
-    unpack_v(p, v);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      x2[i] = mad24(x1[i], x1[i], 0u);
-      x1[i] = v[i] | (x1[i] << 8);
-    }
-  }
-}
-
-template <Walk kW>
-__device__ inline void unpack_y(const uint4 p, uint32_t (&y)[8]) {
-  if (kW == kNXandXX)
-    unpack_v(p, y);
-  else if (kW == kYY)
-    unpack_qq(p, y);
-  else
-    unpack_q(p, y);
-}
-
-// 8 rows x 8 lags: x = rows t .. t + 7, (ya, yb) = rows t + k0 .. t + k0 + 15; every factor is below 2^24
-template <Walk kW>
-__device__ inline void mac(const uint32_t (&x1)[8], const uint32_t (&x2)[8], const uint32_t (&ya)[8], const uint32_t (&yb)[8],
-                           uint32_t (&p1)[kKT], uint32_t (&p2)[kKT]) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-#pragma unroll
-    for (int j = 0; j < int(kKT); ++j) {
-      const int e = i + j;
-      const uint32_t y = e < 8 ? ya[e & 7] : yb[e & 7];
-      p1[j] = mad24(x1[i], y, p1[j]);
-      if (kW == kXYandY || kW == kNXandXX) p2[j] = mad24(x2[i], y, p2[j]);
-    }
-  }
-}
 
 struct Sums {  // one thread's: n, Sx and Sy of a whole span fit 32 bits
   uint32_t n[kKT] = {}, sx[kKT] = {}, sy[kKT] = {};
@@ -346,8 +251,6 @@ __global__ __launch_bounds__(kNT) void xcorr_ring_kernel(const XcorrArgs a) {
   }
 }
 
-inline bool pow2(uint64_t x) { return x != 0 && (x & (x - 1)) == 0; }
-
 // the pairs p of one ring of `depth` rows over its span [head - min(n, span), head) onto dst (already
 // zeroed); share 0: xcorr_share's rule, else the chunks of a workgroup, checked by the caller
 inline int run(const XcorrRingPairs& p, const float* base, uint32_t stride, uint64_t depth, uint64_t head, uint64_t n,
@@ -379,17 +282,6 @@ inline int run(const XcorrRingPairs& p, const float* base, uint32_t stride, uint
 inline hipError_t zero(int64_t* dst, uint32_t K, uint32_t L, hipStream_t stream) {
   return hipMemsetAsync(dst, 0, size_t(K) * (2 * L + 1) * kXcorrWords * sizeof(int64_t), stream);
 }
-
-struct DeviceScope {  // the calling thread's device, restored on exit
-  int prev = -1, dev;
-  explicit DeviceScope(int d) : dev(d) {
-    (void)hipGetDevice(&prev);
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceScope() {
-    if (prev >= 0 && prev != dev) (void)hipSetDevice(prev);
-  }
-};
 
 }  // namespace
 

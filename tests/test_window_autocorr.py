@@ -180,7 +180,7 @@ def test_parse_and_check_autocorr():
 def test_constants_mirror_the_header():
     from rocmdash.ops import window_autocorr as wa
 
-    text = open(os.path.join(ROOT, "csrc", "window_autocorr.h")).read() + open(os.path.join(ROOT, "csrc", "window_autocorr.hip")).read()
+    text = "".join(open(os.path.join(ROOT, "csrc", f)).read() for f in ("window_autocorr.h", "window_lag_dev.h", "window_autocorr.hip"))
 
     def const(name):
         """``constexpr <type> name = 123;`` or ``= 1u << 6;`` - nothing else is understood."""

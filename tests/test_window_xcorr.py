@@ -201,7 +201,7 @@ def test_parse_and_check_xcorr():
 def test_constants_mirror_the_header():
     from rocmdash.ops import window_autocorr as wa, window_joint as wj, window_xcorr as wx
 
-    text = open(os.path.join(ROOT, "csrc", "window_xcorr_plan.h")).read() + open(os.path.join(ROOT, "csrc", "window_xcorr.hip")).read()
+    text = "".join(open(os.path.join(ROOT, "csrc", f)).read() for f in ("window_xcorr_plan.h", "window_lag_dev.h", "window_xcorr.hip"))
 
     def const(name):
         m = re.search(rf"constexpr \w+ {name} = (?:(\d+)u?|1u << (\d+));", text)
